@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- Pixie pixel-SOM train + assign throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
     (N > 1 without RANK in the environment: re-executes itself under torch.distributed.run, one rank per GPU;
      fails loudly when the box has fewer than N devices)
 
@@ -93,10 +93,36 @@ def parse():
                          "config 2) instead of ONE pass over x (pxsom_assign_sums: 0.36 ms, fixed-point workgroup tables; the "
                          "default since round 3)")
     ap.add_argument("--no-operating-range", action="store_true", help="skip the operating-range legs (data-row / near-tie codebooks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (codebook, labels, per-cluster counts and "
+                         "means; rank 0's with --gpus N) as DIR/<name>.npy, float32 / float64, for output-for-output comparison of builds")
     ap.add_argument("--pmc-inner", action="store_true", help=argparse.SUPPRESS)   # the run rocprofv3 wraps
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     a.one_pass = not a.two_pass
     return a
+
+
+DUMP_ROWS_MAX = 12 << 20       # per-row outputs up to this many rows are written whole (labels as float32: 48 MiB) ...
+DUMP_SAMPLE_ROWS = 4 << 20     # ... longer ones as this fixed, seeded sample of rows, their indices beside them: < 64 MB in all
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy -- binary64 and int64 as float64, everything else as float32 (labels are
+    node ids < 2^24: exact).  An array of more than DUMP_ROWS_MAX rows is written as the rows of one seeded sample (the same
+    rows in every run of the same arguments), with their indices in out_dir/<name>_rows.npy.  Run to run, codebook, labels and
+    counts are the same bits; the per-cluster means may differ in the last place (the one-pass kernel's workgroup tables are
+    added into binary64 sums in a run-dependent order, include/pxsom.h), so compare those within a tolerance."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        t = torch.as_tensor(a)
+        if t.shape[0] > DUMP_ROWS_MAX:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], DUMP_SAMPLE_ROWS, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        wide = t.dtype in (torch.float64, torch.int64)
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float64 if wide else np.float32))
 
 
 def respawn_under_torchrun(args):
@@ -248,6 +274,9 @@ def run_cfg1(args):
             if i >= args.warmup:
                 times.append(t)
         legs[mode] = (np.mean(np.asarray(times), axis=0), w, lab, avg)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, **{mode + "_codebook": w, mode + "_labels": np.asarray(lab),
+                                               mode + "_cluster_means": avg[chans].to_numpy(np.float64)})
     line = {"metric": "M pixels/sec SOM train+assign through the drop-in pipeline functions, 1 FOV 512x512x8ch, 100-node SOM",
             "unit": "Mpx/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -407,6 +436,8 @@ def main():
         fence()
         t1 = time.perf_counter()
         kern_ms, kern_launches = timer.collect()
+    if args.dump_outputs and rank == 0 and not args.pmc_inner:     # before the phase run below overwrites them
+        dump_outputs(args.dump_outputs, codebook=w, labels=labels, cluster_counts=k8_counts, cluster_means=means)
     # the phases of a step: the same K steps once more, with an event pair around each half (four event records per step cost the
     # stream 10 - 15 us: they are not part of the step and stay out of the timed region)
     for i in range(args.steps):

@@ -23,14 +23,9 @@ import sys
 import numpy as np
 
 
-def main():
-    try:
-        import pyFlowSOM
-        from pyFlowSOM import map_data_to_nodes, som
-    except Exception as err:   # noqa: BLE001
-        sys.exit("pyFlowSOM is not importable here (%s): run this where `pip install pyFlowSOM==0.1.16` works" % err)
-    out = {"pyflowsom_version": np.array(getattr(pyFlowSOM, "__version__", "unknown")),
-           "numpy_version": np.array(np.__version__)}
+def case_inputs():
+    """(tag, x, xdim, ydim, rlen, seed) of every case: inputs only, the same wherever this runs (numpy's RandomState).
+    tests/test_pyflowsom_vectors.py runs the same cases."""
     cases = []
     for c in (4, 22, 40):
         for (xdim, ydim) in ((10, 10), (20, 20)):
@@ -41,19 +36,37 @@ def main():
     cases.append((22, 10, 10, 2, 11, True))
     cases.append((8, 10, 10, 3, 12, True))
     for idx, (c, xdim, ydim, rlen, seed, clipped) in enumerate(cases):
-        tag = "case%02d" % idx
         rs = np.random.RandomState(1000 + idx)
         n = 1500 if xdim == 10 else 2400
         x = rs.gamma(0.7, 0.4, size=(n, c))
         x[rs.rand(n, c) < 0.2] = 0.0
         if clipped:
             x = np.minimum(x, 0.9)
-        x = np.ascontiguousarray(x, dtype=np.float64)
+        yield "case%02d" % idx, np.ascontiguousarray(x, dtype=np.float64), xdim, ydim, rlen, seed
+
+
+def rows_to_label(x, codes):
+    """The rows each case labels: 600 data rows, nodes 0 and 3, the midpoint of nodes 3 and 4."""
+    return np.concatenate([x[:600], codes[[0, 3]], 0.5 * (codes[3:4] + codes[4:5])])
+
+
+def main():
+    try:
+        import pyFlowSOM
+        from pyFlowSOM import map_data_to_nodes, som
+    except Exception as err:   # noqa: BLE001
+        sys.exit("pyFlowSOM is not importable here (%s): run this where `pip install pyFlowSOM==0.1.16` works" % err)
+    out = {"pyflowsom_version": np.array(getattr(pyFlowSOM, "__version__", "unknown")),
+           "numpy_version": np.array(np.__version__)}
+    n_cases = 0
+    for tag, x, xdim, ydim, rlen, seed in case_inputs():
+        n_cases += 1
+        n, c = x.shape
         codes = som(x, xdim=xdim, ydim=ydim, rlen=rlen, alpha_range=(0.05, 0.01), seed=seed)
         codes = np.asarray(codes, dtype=np.float64).reshape(xdim * ydim, -1)
         codes_again = np.asarray(som(x, xdim=xdim, ydim=ydim, rlen=rlen, alpha_range=(0.05, 0.01), seed=seed),
                                  dtype=np.float64).reshape(xdim * ydim, -1)
-        test = np.concatenate([x[:600], codes[[0, 3]], 0.5 * (codes[3:4] + codes[4:5])])
+        test = rows_to_label(x, codes)
         tie_codes = codes.copy()
         tie_codes[-1] = tie_codes[len(tie_codes) // 2]              # an exact tie pair: which label comes back?
         labels, dists = map_data_to_nodes(codes, test)
@@ -76,11 +89,11 @@ def main():
             out[tag + "_nan_label"] = np.asarray(nl).astype(np.int64)
         except Exception:   # noqa: BLE001
             pass
-    out["n_cases"] = np.array(len(cases), dtype=np.int64)
+    out["n_cases"] = np.array(n_cases, dtype=np.int64)
     here = os.path.dirname(os.path.abspath(__file__))
     path = os.path.join(os.path.dirname(here), "tests", "golden", "g11_pyflowsom.npz")
     np.savez_compressed(path, **out)
-    print("wrote", path, "with", len(cases), "cases from pyFlowSOM", out["pyflowsom_version"])
+    print("wrote", path, "with", n_cases, "cases from pyFlowSOM", out["pyflowsom_version"])
 
 
 if __name__ == "__main__":

@@ -33,7 +33,7 @@ import scipy.ndimage as ndimage  # noqa: E402
 from tests import oracle_binding as ob  # noqa: E402
 
 
-OUT_DIR = os.environ.get("PXSOM_GOLDEN_OUT", HERE)     # tests/test_golden_regenerates.py writes to a scratch directory
+OUT_DIR = os.environ.get("PXSOM_GOLDEN_OUT", HERE)     # a scratch directory, to compare a regeneration with the committed files
 
 
 def save(name, **arrays):

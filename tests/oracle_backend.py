@@ -127,3 +127,12 @@ def install(patch):
     patch(flowsom, "positive_quantile_f32", positive_quantile_f32)
     patch(flowsom, "total_intensity_quantile_f32", total_intensity_quantile_f32)
     patch(flowsom, "_batch_backend", lambda: (torch.device("cpu"), OracleKernels()))
+
+
+def join_cpu_group(rank, world):
+    """The process group of a multi-rank CPU test's worker, where a HIP device is visible: gloo, joined before the pipeline's own
+    distributed.init_from_env would join "nccl" with LOCAL_RANK as the device (rank 1 of a one-GPU box has none).  Without a
+    device nothing is joined here: init_from_env joins gloo itself, as these tests check."""
+    if torch.cuda.is_available():
+        import torch.distributed as dist
+        dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -39,6 +39,7 @@ def _worker(rank, world, port, td, mode, out_path, fovs=None, kernels="oracle"):
     if kernels == "oracle":
         from tests import oracle_backend
         oracle_backend.install(setattr)
+        oracle_backend.join_cpu_group(rank, world)
     else:
         # the HIP path on ONE device shared by the ranks: RCCL refuses two ranks on a GPU, so the group is gloo
         # (joined here, before the pipeline's own init_from_env would pick "nccl")
@@ -234,6 +235,7 @@ def _matrix_worker(rank, world, port, td, out_path, kernels="oracle"):
     if kernels == "oracle":
         from tests import oracle_backend
         oracle_backend.install(setattr)
+        oracle_backend.join_cpu_group(rank, world)
     else:     # both ranks on device 0: the group has to be gloo (joined before init_from_env would pick "nccl")
         import torch
         torch.cuda.set_device(0)

@@ -1,7 +1,9 @@
 """Consumes tests/golden/g11_pyflowsom.npz -- vectors dumped from the REAL pyFlowSOM 0.1.16 by
 scripts/dump_pyflowsom_vectors.py -- when that file exists; skipped otherwise (pyFlowSOM is absent from the build
 image: SOM parity is "unpinned" until somebody runs the dump script where the package installs and commits the
-file).  CPU: the oracle; -m gpu: the HIP path through ark_analysis_amd.flowsom.
+file).  CPU: the oracle; -m gpu: the HIP path through ark_analysis_amd.flowsom -- which, until the file exists, is held
+against the oracle on the same cases instead, so that the device half of the parity chain is pinned on exactly the
+inputs the vectors will carry.
 
 map_data_to_nodes needs no recollection beyond the arithmetic (labels + distances must be equal, bit for bit).
 som() additionally depends on the recalled seed -> (initial nodes, order) mapping and on a handful of recalled
@@ -13,7 +15,8 @@ import os
 import numpy as np
 import pytest
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g11_pyflowsom.npz")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "g11_pyflowsom.npz")
 needs_vectors = pytest.mark.skipif(not os.path.exists(GOLD), reason="tests/golden/g11_pyflowsom.npz not present "
                                    "(run scripts/dump_pyflowsom_vectors.py where pyFlowSOM==0.1.16 installs)")
 
@@ -79,17 +82,43 @@ def test_oracle_training_equals_pyflowsom(oracle):
                         % (tag, seed, _sweep(oracle, g, tag, x[init_idx], g[tag + "_codes"])))
 
 
-@needs_vectors
-@pytest.mark.gpu
-def test_hip_path_equals_pyflowsom(gpu):
+def _hip_cases(oracle):
+    """(tag, x, (xdim, ydim, rlen, seed), codes, test rows, labels, distances) the HIP path must reproduce: pyFlowSOM's own
+    outputs where g11 is committed; until then the oracle's on the same inputs (the cases of scripts/dump_pyflowsom_vectors.py),
+    which the two tests above hold against pyFlowSOM once the file exists."""
+    if os.path.exists(GOLD):
+        for tag, g in _cases():
+            grid = tuple(int(v) for v in g[tag + "_grid"])
+            yield tag, g[tag + "_x"], grid, g[tag + "_codes"], g[tag + "_test"], g[tag + "_labels"], g[tag + "_dists"]
+        return
+    import importlib.util
     from ark_analysis_amd import flowsom
-    for tag, g in _cases():
-        xdim, ydim, rlen, seed = (int(v) for v in g[tag + "_grid"])
-        labels, dists = flowsom.map_data_to_nodes(g[tag + "_codes"], g[tag + "_test"])
-        np.testing.assert_array_equal(labels, g[tag + "_labels"], err_msg=tag)
-        np.testing.assert_array_equal(dists, g[tag + "_dists"], err_msg=tag)
-        codes = flowsom.som(g[tag + "_x"], xdim=xdim, ydim=ydim, rlen=rlen, alpha_range=(0.05, 0.01), seed=seed)
-        np.testing.assert_array_equal(np.asarray(codes).reshape(xdim * ydim, -1), g[tag + "_codes"], err_msg=tag)
+    spec = importlib.util.spec_from_file_location("dump_pyflowsom_vectors", os.path.join(ROOT, "scripts", "dump_pyflowsom_vectors.py"))
+    dump = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(dump)
+    for tag, x, xdim, ydim, rlen, seed in dump.case_inputs():
+        init_idx, order = flowsom.som_init_and_order(len(x), xdim * ydim, rlen, seed)
+        codes = oracle.som_online(x, x[init_idx].copy(), xdim, ydim, rlen, (0.05, 0.01), flowsom.default_radius_range(xdim, ydim),
+                                  order)
+        test = dump.rows_to_label(x, codes)
+        labels, dists = oracle.map_data_to_nodes(codes, test)
+        yield tag, x, (xdim, ydim, rlen, seed), codes, test, labels, dists
+
+
+@pytest.mark.gpu
+def test_hip_path_equals_pyflowsom(gpu, oracle):
+    """flowsom.map_data_to_nodes and flowsom.som(..., seed) on the HIP path, bit for bit, on every vector case (see
+    _hip_cases: against pyFlowSOM where its vectors are committed, else against the oracle on the same inputs)."""
+    from ark_analysis_amd import flowsom
+    n = 0
+    for tag, x, (xdim, ydim, rlen, seed), want_codes, test, want_labels, want_dists in _hip_cases(oracle):
+        labels, dists = flowsom.map_data_to_nodes(want_codes, test)
+        np.testing.assert_array_equal(labels, want_labels, err_msg=tag)
+        np.testing.assert_array_equal(dists, want_dists, err_msg=tag)
+        codes = flowsom.som(x, xdim=xdim, ydim=ydim, rlen=rlen, alpha_range=(0.05, 0.01), seed=seed)
+        np.testing.assert_array_equal(np.asarray(codes).reshape(xdim * ydim, -1), want_codes, err_msg=tag)
+        n += 1
+    assert n > 0
 
 
 def test_recalled_switches_are_wired(oracle):
