@@ -16,6 +16,12 @@ PXSOM_F64 = 1
 PXSOM_F16 = 2
 MAX_CHANNELS = 1024
 MAX_NODES = 1024
+# FlowSOM's distf codes (include/pxsom.h PXSOM_METRIC_*)
+METRIC_MANHATTAN = 1
+METRIC_EUCLIDEAN = 2
+METRIC_CHEBYSHEV = 3
+METRIC_COSINE = 4
+METRICS = (METRIC_MANHATTAN, METRIC_EUCLIDEAN, METRIC_CHEBYSHEV, METRIC_COSINE)
 
 _STATUS = {0: "PXSOM_OK", -1: "PXSOM_ERR_INVALID_ARG", -2: "PXSOM_ERR_UNSUPPORTED",
            -3: "PXSOM_ERR_WORKSPACE", -4: "PXSOM_ERR_HIP"}
@@ -90,6 +96,10 @@ SYMBOLS = {
     "pxsom_comm_p2p_connect": (_i32, [_vp, _vp, _sz]),
     "pxsom_comm_p2p_error": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     "pxsom_comm_p2p_set_fused": (_i32, [_vp, _i32]),
+    "pxsom_assign_metric_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "pxsom_assign_metric": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _i32, _vp]),
+    "pxsom_train_online_metric": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i32, _i32, _i32, _f64, _f64,
+                                         _f64, _f64, _vp, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -18,6 +18,7 @@
 
 #include "pxsom_assign.h"
 #include "pxsom_common.h"
+#include "pxsom_metric.h"
 #include "pxsom_sums.h"
 #include "pxsom_wave.h"
 #include "pxsom_xch.h"
@@ -51,7 +52,8 @@ __device__ __forceinline__ double change_term(double tmp, int flags)
     return ((flags & PXSOM_ONLINE_INT_ABS) && fabs(tmp) < 2147483648.0) ? (double)abs((int)tmp) : fabs(tmp);
 }
 
-template <typename T, int CMAX, int MAXT, bool GLB = false>
+// M: the BMU distance (PXSOM_METRIC_*); every other part of the loop is the same for all of them.
+template <typename T, int CMAX, int MAXT, bool GLB = false, int M = PXSOM_METRIC_EUCLIDEAN>
 __global__ __launch_bounds__(MAXT) void som_online_kernel(const T *__restrict__ x, int64_t n, int c,
                                                           int64_t ldx, double *w, int xdim, int ydim,
                                                           int rlen, double a0, double a1, double r0,
@@ -171,78 +173,129 @@ __global__ __launch_bounds__(MAXT) void som_online_kernel(const T *__restrict__ 
                 mychange = 0.0;
             }
             const double *xr = xc + (size_t)s * cs;
-            // squared distance of this thread's node (binary64, j ascending) -- FlowSOM eucl() before
-            // its sqrt.  The oracle compares sqrt(d2) values with a strict '<' (first minimum wins).
-            // sqrt is monotone, so whenever the smallest d2 is isolated by more than a few ulps its
-            // node is the answer and no sqrt is evaluated; only near-coincident candidates (d2 within
-            // 2^-50 relative of the minimum) take the sqrt path, which reproduces the oracle's ties.
             double xreg[REG ? CMAX : 1];
-            double d2 = INFINITY;
-            if constexpr (REG) {
+            int nearest;
+            if constexpr (M == PXSOM_METRIC_EUCLIDEAN) {
+                // squared distance of this thread's node (binary64, j ascending) -- FlowSOM eucl() before
+                // its sqrt.  The oracle compares sqrt(d2) values with a strict '<' (first minimum wins).
+                // sqrt is monotone, so whenever the smallest d2 is isolated by more than a few ulps its
+                // node is the answer and no sqrt is evaluated; only near-coincident candidates (d2 within
+                // 2^-50 relative of the minimum) take the sqrt path, which reproduces the oracle's ties.
+                double d2 = INFINITY;
+                if constexpr (REG) {
 #pragma unroll
-                for (int j = 0; j < CMAX; j++) xreg[j] = xr[j];  // one burst of broadcast LDS reads
-                double xdist = 0.0;
+                    for (int j = 0; j < CMAX; j++) xreg[j] = xr[j];  // one burst of broadcast LDS reads
+                    double xdist = 0.0;
 #pragma unroll
-                for (int j = 0; j < CMAX; j++) {
-                    const double tmp = xreg[j] - wr[j];  // pad slots: 0 - 0
-                    xdist += tmp * tmp;
-                }
-                if (has_node && xdist == xdist) d2 = xdist;
-            } else if (has_node) {
-                double xdist = 0.0;
-                for (int j = 0; j < c; j++) {
-                    const double tmp = xr[j] - wref(j);
-                    xdist += tmp * tmp;
-                }
-                if (xdist == xdist) d2 = xdist;
-            }
-            const double near_eps = 8.881784197001252e-16;  // 2^-50
-            double wmin = wave_min_f64(d2);
-            unsigned long long cand = __ballot(d2 <= wmin + wmin * near_eps);
-            int bk;
-            double bd2;
-            if (__popcll(cand) == 1) {
-                bk = (wv << 6) + (int)__ffsll((long long)cand) - 1;
-                bd2 = wmin;
-            } else {
-                const double sd = sqrt(d2);
-                const double smin = wave_min_f64(sd);
-                cand = __ballot(sd == smin);
-                const int first = cand ? (int)__ffsll((long long)cand) - 1 : 0;
-                bk = (wv << 6) + first;
-                bd2 = __shfl(d2, first);
-            }
-            if (bk >= K) bk = 0x7fffffff;  // only padding lanes (all-infinite wave)
-            int nearest = bk;
-            if (nwv > 1) {
-                if (lane == 0) {
-                    exd[par * nwv + wv] = bd2;
-                    exk[par * nwv + wv] = bk;
-                }
-                __syncthreads();
-                double gmin = exd[par * nwv];
-                for (int i = 1; i < nwv; i++) gmin = fmin(gmin, exd[par * nwv + i]);
-                const double lim = gmin + gmin * near_eps;
-                int ncand = 0;
-                for (int i = 0; i < nwv; i++) {
-                    if (exd[par * nwv + i] <= lim) {
-                        if (ncand == 0) nearest = exk[par * nwv + i];
-                        ncand++;
+                    for (int j = 0; j < CMAX; j++) {
+                        const double tmp = xreg[j] - wr[j];  // pad slots: 0 - 0
+                        xdist += tmp * tmp;
                     }
+                    if (has_node && xdist == xdist) d2 = xdist;
+                } else if (has_node) {
+                    double xdist = 0.0;
+                    for (int j = 0; j < c; j++) {
+                        const double tmp = xr[j] - wref(j);
+                        xdist += tmp * tmp;
+                    }
+                    if (xdist == xdist) d2 = xdist;
                 }
-                if (ncand > 1) {  // near-coincident minima in different waves: compare like the oracle
-                    double best = INFINITY;
-                    nearest = 0x7fffffff;
+                const double near_eps = 8.881784197001252e-16;  // 2^-50
+                double wmin = wave_min_f64(d2);
+                unsigned long long cand = __ballot(d2 <= wmin + wmin * near_eps);
+                int bk;
+                double bd2;
+                if (__popcll(cand) == 1) {
+                    bk = (wv << 6) + (int)__ffsll((long long)cand) - 1;
+                    bd2 = wmin;
+                } else {
+                    const double sd = sqrt(d2);
+                    const double smin = wave_min_f64(sd);
+                    cand = __ballot(sd == smin);
+                    const int first = cand ? (int)__ffsll((long long)cand) - 1 : 0;
+                    bk = (wv << 6) + first;
+                    bd2 = __shfl(d2, first);
+                }
+                if (bk >= K) bk = 0x7fffffff;  // only padding lanes (all-infinite wave)
+                nearest = bk;
+                if (nwv > 1) {
+                    if (lane == 0) {
+                        exd[par * nwv + wv] = bd2;
+                        exk[par * nwv + wv] = bk;
+                    }
+                    __syncthreads();
+                    double gmin = exd[par * nwv];
+                    for (int i = 1; i < nwv; i++) gmin = fmin(gmin, exd[par * nwv + i]);
+                    const double lim = gmin + gmin * near_eps;
+                    int ncand = 0;
                     for (int i = 0; i < nwv; i++) {
-                        const double sdi = sqrt(exd[par * nwv + i]);
-                        const int ki = exk[par * nwv + i];
-                        if (sdi < best || (sdi == best && ki < nearest)) {
-                            best = sdi;
-                            nearest = ki;
+                        if (exd[par * nwv + i] <= lim) {
+                            if (ncand == 0) nearest = exk[par * nwv + i];
+                            ncand++;
                         }
                     }
+                    if (ncand > 1) {  // near-coincident minima in different waves: compare like the oracle
+                        double best = INFINITY;
+                        nearest = 0x7fffffff;
+                        for (int i = 0; i < nwv; i++) {
+                            const double sdi = sqrt(exd[par * nwv + i]);
+                            const int ki = exk[par * nwv + i];
+                            if (sdi < best || (sdi == best && ki < nearest)) {
+                                best = sdi;
+                                nearest = ki;
+                            }
+                        }
+                    }
+                    par ^= 1;
                 }
-                par ^= 1;
+            } else {
+                // FlowSOM's selection: nearest starts at node 0 and moves on `d[k] < d[nearest]` -- the first minimum over
+                // the non-NaN distances, or node 0 when its own distance is NaN.  Keys: NaN -> +inf, node 0's NaN -> -inf
+                // (exact comparisons from here on: the first lane / wave holding the minimum key is the oracle's node)
+                double d = INFINITY;
+                if constexpr (REG) {
+#pragma unroll
+                    for (int j = 0; j < CMAX; j++) xreg[j] = xr[j];
+                    double acc = 0.0, d1 = 0.0, d2w = 0.0;
+#pragma unroll
+                    for (int j = 0; j < CMAX; j++) {  // pad slots: x = w = 0 leaves every accumulator unchanged
+                        acc = pxsom_metric::term<M>(acc, xreg[j], wr[j]);
+                        if constexpr (M == PXSOM_METRIC_COSINE) {
+                            d1 = pxsom_metric::square_add(d1, xreg[j]);
+                            d2w = pxsom_metric::square_add(d2w, wr[j]);
+                        }
+                    }
+                    d = pxsom_metric::finish<M>(acc, sqrt(d1), sqrt(d2w));
+                } else {
+                    double acc = 0.0, d1 = 0.0, d2w = 0.0;
+                    if (has_node) {
+                        for (int j = 0; j < c; j++) {
+                            const double wj = wref(j);
+                            acc = pxsom_metric::term<M>(acc, xr[j], wj);
+                            if constexpr (M == PXSOM_METRIC_COSINE) {
+                                d1 = pxsom_metric::square_add(d1, xr[j]);
+                                d2w = pxsom_metric::square_add(d2w, wj);
+                            }
+                        }
+                    }
+                    d = pxsom_metric::finish<M>(acc, sqrt(d1), sqrt(d2w));
+                }
+                const double key = !has_node ? INFINITY : d == d ? d : node == 0 ? -INFINITY : INFINITY;
+                const double wmin = wave_min_f64(key);
+                const unsigned long long cand = __ballot(key == wmin);
+                nearest = (wv << 6) + (int)__ffsll((long long)cand) - 1;
+                if (nwv > 1) {
+                    if (lane == 0) {
+                        exd[par * nwv + wv] = wmin;
+                        exk[par * nwv + wv] = nearest;
+                    }
+                    __syncthreads();
+                    double gmin = exd[par * nwv];
+                    for (int i = 1; i < nwv; i++) gmin = fmin(gmin, exd[par * nwv + i]);
+                    for (int i = nwv - 1; i >= 0; i--)
+                        if (exd[par * nwv + i] == gmin) nearest = exk[par * nwv + i];
+                    par ^= 1;
+                }
             }
             if (nearest >= K) nearest = 0;
             if (threshold < 1.0) threshold = 0.5;
@@ -984,7 +1037,7 @@ __global__ __launch_bounds__(NT) void cluster_sums_kernel(const T *__restrict__ 
     }
 }
 
-template <typename T, int CMAX, int MAXT>
+template <typename T, int CMAX, int MAXT, int M = PXSOM_METRIC_EUCLIDEAN>
 int launch_online(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen, double a0,
                   double a1, double r0, double r1, const int64_t *order, int flags, hipStream_t st)
 {
@@ -1022,9 +1075,9 @@ int launch_online(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim
         return PXSOM_OK;
     };
     if constexpr (CMAX == 0) {
-        if (in_place) return launch(som_online_kernel<T, CMAX, MAXT, true>);
+        if (in_place) return launch(som_online_kernel<T, CMAX, MAXT, true, M>);
     }
-    return launch(som_online_kernel<T, CMAX, MAXT, false>);
+    return launch(som_online_kernel<T, CMAX, MAXT, false, M>);
 }
 
 template <typename T, int CH, int L>
@@ -1094,6 +1147,40 @@ int train_online_typed(const T *x, int64_t n, int c, int64_t ldx, double *w, int
     }
     PXSOM_ONLINE(0, 1024);  // more nodes or wider rows: 128 VGPRs per thread, codebook stays in LDS
 #undef PXSOM_ONLINE
+}
+
+// Manhattan, Chebyshev, cosine: thread <-> node for every shape (the split kernel's several lanes per node would sum a
+// node's channels out of the oracle's order); fewer register widths than the Euclidean route -- pad slots add exact zeros
+template <typename T, int M>
+int train_online_metric_typed(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen,
+                              double a0, double a1, double r0, double r1, const int64_t *order, int flags, hipStream_t st)
+{
+#define PXSOM_ONLINE_M(CM, MT) \
+    return launch_online<T, CM, MT, M>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st)
+    if (xdim * ydim <= 256) {
+        if (c <= 8) PXSOM_ONLINE_M(8, 256);
+        if (c <= 24) PXSOM_ONLINE_M(24, 256);
+        if (c <= 40) PXSOM_ONLINE_M(40, 256);
+        if (c <= 64) PXSOM_ONLINE_M(64, 256);
+        PXSOM_ONLINE_M(0, 256);
+    }
+    if (xdim * ydim <= 512) {
+        if (c <= 16) PXSOM_ONLINE_M(16, 512);
+        if (c <= 40) PXSOM_ONLINE_M(40, 512);
+    }
+    PXSOM_ONLINE_M(0, 1024);
+#undef PXSOM_ONLINE_M
+}
+
+template <typename T>
+int train_online_metric(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen, double a0,
+                        double a1, double r0, double r1, const int64_t *order, int metric, int flags, hipStream_t st)
+{
+    if (metric == PXSOM_METRIC_MANHATTAN)
+        return train_online_metric_typed<T, PXSOM_METRIC_MANHATTAN>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st);
+    if (metric == PXSOM_METRIC_CHEBYSHEV)
+        return train_online_metric_typed<T, PXSOM_METRIC_CHEBYSHEV>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st);
+    return train_online_metric_typed<T, PXSOM_METRIC_COSINE>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1405,21 +1492,35 @@ int check_matrix(const char *fn, const void *x, int64_t n, int c, int64_t ldx, i
     return PXSOM_OK;
 }
 
+// arguments of an online training call; *nothing_to_do: valid, and no step to run (n == 0 or rlen == 0)
+int check_online(const char *fn, const void *x, int64_t n, int c, int64_t ldx, int dtype, const double *w, int xdim,
+                 int ydim, int rlen, const int64_t *order, int flags, bool *nothing_to_do)
+{
+    *nothing_to_do = false;
+    int rc = check_matrix(fn, x, n, c, ldx, dtype);
+    if (rc) return rc;
+    if (xdim < 1 || ydim < 1 || (int64_t)xdim * ydim > PXSOM_MAX_NODES)
+        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "%s: grid %dx%d outside [1, %d] nodes", fn, xdim, ydim, PXSOM_MAX_NODES);
+    if (rlen < 0 || !w) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad rlen / null codebook", fn);
+    if (flags & ~PXSOM_ONLINE_INT_ABS) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: unknown flags %d", fn, flags);
+    if (n == 0 || rlen == 0) {
+        *nothing_to_do = true;
+        return PXSOM_OK;
+    }
+    if (!order) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: null order", fn);
+    return PXSOM_OK;
+}
+
 }  // namespace
 
 PXSOM_EXPORT int pxsom_train_online_ex(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, double *w_dev,
                                        int xdim, int ydim, int rlen, double a0, double a1, double r0, double r1,
                                        const int64_t *order_dev, int flags, void *stream)
 {
-    int rc = check_matrix("pxsom_train_online", x_dev, n, c, ldx, dtype);
-    if (rc) return rc;
-    if (xdim < 1 || ydim < 1 || (int64_t)xdim * ydim > PXSOM_MAX_NODES)
-        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_train_online: grid %dx%d outside [1, %d] nodes", xdim,
-                           ydim, PXSOM_MAX_NODES);
-    if (rlen < 0 || !w_dev) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_train_online: bad rlen / null codebook");
-    if (flags & ~PXSOM_ONLINE_INT_ABS) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_train_online: unknown flags %d", flags);
-    if (n == 0 || rlen == 0) return PXSOM_OK;
-    if (!order_dev) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_train_online: null order");
+    bool nothing_to_do = false;
+    int rc = check_online("pxsom_train_online", x_dev, n, c, ldx, dtype, w_dev, xdim, ydim, rlen, order_dev, flags,
+                          &nothing_to_do);
+    if (rc || nothing_to_do) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     PXSOM_DISPATCH_DTYPE(dtype, x_dev, xp,
                          train_online_typed<T>(xp, n, c, ldx, w_dev, xdim, ydim, rlen, a0, a1, r0, r1, order_dev, flags, st));
@@ -1430,6 +1531,26 @@ PXSOM_EXPORT int pxsom_train_online(const void *x_dev, int64_t n, int c, int64_t
                                     const int64_t *order_dev, void *stream)
 {
     return pxsom_train_online_ex(x_dev, n, c, ldx, dtype, w_dev, xdim, ydim, rlen, a0, a1, r0, r1, order_dev, 0, stream);
+}
+
+PXSOM_EXPORT int pxsom_train_online_metric(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, double *w_dev,
+                                           int xdim, int ydim, int rlen, double a0, double a1, double r0, double r1,
+                                           const int64_t *order_dev, int metric, int flags, void *stream)
+{
+    if (metric < PXSOM_METRIC_MANHATTAN || metric > PXSOM_METRIC_COSINE)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG,
+                           "pxsom_train_online_metric: unknown metric %d (FlowSOM distf: 1 Manhattan, 2 Euclidean, "
+                           "3 Chebyshev, 4 cosine)", metric);
+    if (metric == PXSOM_METRIC_EUCLIDEAN)
+        return pxsom_train_online_ex(x_dev, n, c, ldx, dtype, w_dev, xdim, ydim, rlen, a0, a1, r0, r1, order_dev, flags, stream);
+    bool nothing_to_do = false;
+    int rc = check_online("pxsom_train_online_metric", x_dev, n, c, ldx, dtype, w_dev, xdim, ydim, rlen, order_dev, flags,
+                          &nothing_to_do);
+    if (rc || nothing_to_do) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    PXSOM_DISPATCH_DTYPE(dtype, x_dev, xp,
+                         (train_online_metric<T>(xp, n, c, ldx, w_dev, xdim, ydim, rlen, a0, a1, r0, r1, order_dev, metric,
+                                                 flags, st)));
 }
 
 PXSOM_EXPORT int pxsom_cluster_sums(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype,

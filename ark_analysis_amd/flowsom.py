@@ -15,6 +15,7 @@ holds (tests/phenotyping/cluster_helpers_test.py:323-332).  This build documents
 Both are explicit inputs of the kernels (BASELINE.json: "given identical init weights and pixel
 presentation order"), see :func:`som_with_inputs`.
 """
+import operator
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -39,7 +40,29 @@ RECALLED = {
     "node_order": ("xy", "node k = x*ydim + y ('yx': k = y*xdim + x)"),
     "change_abs": ("fabs", "the early-stop accumulator adds fabs(x - w) ('int_abs': C's integer abs(), which truncates "
                            "every |x - w| < 1 to 0 -- a run with rlen >= 2 on normalised data then stops at its second pass)"),
+    "distances": ({1: "manhattan", 2: "euclidean", 3: "chebyshev", 4: "cosine"},
+                  "distf codes and formulas of FlowSOM's som.c, binary64, channels ascending, one rounding per operation: "
+                  "1 d += fabs(x - w); 2 sqrt(sum (x - w)^2); 3 t = fabs(x - w), if (t > d) d = t (NaN channels skipped); "
+                  "4 nom += x*w, d1 += x*x, d2 += w*w, d = -nom / (sqrt(d1) * sqrt(d2)) + 1 -- parity with pyFlowSOM "
+                  "unpinned, as for Euclidean"),
 }
+
+#: FlowSOM ``distf`` codes this build runs (:data:`RECALLED` ``"distances"``)
+DISTF_CODES = (1, 2, 3, 4)
+
+
+def _check_distf(distf) -> int:
+    """The integer code (Python or numpy integers; not bool, not float) or NotImplementedError."""
+    code = None
+    if not isinstance(distf, (bool, np.bool_)):
+        try:
+            code = operator.index(distf)
+        except TypeError:
+            pass
+    if code not in DISTF_CODES:
+        raise NotImplementedError(f"distf={distf!r} is not built: FlowSOM's distf 1 (Manhattan), 2 (Euclidean), "
+                                  f"3 (Chebyshev) and 4 (cosine) are")
+    return code
 
 
 def default_radius_range(xdim: int, ydim: int, quantile: Optional[float] = None) -> Tuple[float, float]:
@@ -81,11 +104,13 @@ def _as_device_matrix(data, device):
 
 def som_with_inputs(data, init_nodes, order, xdim: int = 10, ydim: int = 10, rlen: int = 10,
                     alpha_range: Sequence[float] = (0.05, 0.01),
-                    radius_range: Optional[Sequence[float]] = None, change_abs: Optional[str] = None) -> np.ndarray:
+                    radius_range: Optional[Sequence[float]] = None, change_abs: Optional[str] = None,
+                    distf: int = 2) -> np.ndarray:
     """Exact online SOM with explicit initial nodes [K, C] and presentation order [n*rlen].  ``change_abs``: one of the
-    alternatives of :data:`RECALLED` (default: the build's reading)."""
+    alternatives of :data:`RECALLED` (default: the build's reading).  ``distf``: FlowSOM's distance code (1-4)."""
     import torch
     from . import _capi, som_device
+    distf = _check_distf(distf)
     dev = _capi.require_gpu()
     x = _as_device_matrix(data, dev)
     w = torch.from_numpy(np.ascontiguousarray(init_nodes, dtype=np.float64)).to(dev)
@@ -95,16 +120,17 @@ def som_with_inputs(data, init_nodes, order, xdim: int = 10, ydim: int = 10, rle
     reading = RECALLED["change_abs"][0] if change_abs is None else change_abs
     if reading not in ("fabs", "int_abs"):
         raise ValueError("unknown change_abs %r" % (reading,))
-    som_device.train_online(x, w, xdim, ydim, rlen, alpha_range, radius_range, od, int_abs=reading == "int_abs")
+    som_device.train_online(x, w, xdim, ydim, rlen, alpha_range, radius_range, od, int_abs=reading == "int_abs",
+                            metric=distf)
     return w.cpu().numpy()
 
 
 def som(data, xdim: int = 10, ydim: int = 10, rlen: int = 10,
         alpha_range: Sequence[float] = (0.05, 0.01), radius_range=None, distf: int = 2,
         nodes=None, importance=None, seed=None) -> np.ndarray:
-    """Drop-in for ``pyFlowSOM.som``: returns the trained codebook [xdim*ydim, C] (float64)."""
-    if distf != 2:
-        raise NotImplementedError("only the Euclidean distance (distf=2) is built; ark uses no other")
+    """Drop-in for ``pyFlowSOM.som``: returns the trained codebook [xdim*ydim, C] (float64).  ``distf``: 1 Manhattan,
+    2 Euclidean, 3 Chebyshev, 4 cosine (:data:`RECALLED` ``"distances"``)."""
+    distf = _check_distf(distf)
     data = np.asarray(data) if not hasattr(data, "is_cuda") else data
     if importance is not None:
         data = np.asarray(data, dtype=np.float64) * np.asarray(importance, dtype=np.float64)
@@ -115,7 +141,7 @@ def som(data, xdim: int = 10, ydim: int = 10, rlen: int = 10,
         src = data[init_idx]
         nodes = src.cpu().numpy() if hasattr(src, "cpu") else np.asarray(src)
     return som_with_inputs(data, np.asarray(nodes, dtype=np.float64), order, xdim, ydim, rlen,
-                           alpha_range, radius_range)
+                           alpha_range, radius_range, distf=distf)
 
 
 def _batch_backend():
@@ -170,17 +196,17 @@ def som_batch(data, xdim: int = 10, ydim: int = 10, rlen: int = 1,
 
 
 def map_data_to_nodes(nodes, newdata, distf: int = 2):
-    """Drop-in for ``pyFlowSOM.map_data_to_nodes``: (labels 1-based, distances) of every row."""
+    """Drop-in for ``pyFlowSOM.map_data_to_nodes``: (labels 1-based, distances) of every row.  ``distf``: 1 Manhattan,
+    2 Euclidean, 3 Chebyshev, 4 cosine (:data:`RECALLED` ``"distances"``)."""
     import torch
     from . import _capi, som_device
-    if distf != 2:
-        raise NotImplementedError("only the Euclidean distance (distf=2) is built; ark uses no other")
+    distf = _check_distf(distf)
     dev = _capi.require_gpu()
     x = _as_device_matrix(newdata, dev)
     if x.dim() == 1:
         x = x.reshape(1, -1)
     w = torch.from_numpy(np.ascontiguousarray(nodes, dtype=np.float64)).to(dev)
-    labels, dists = som_device.assign(x, w, want_dists=True)
+    labels, dists = som_device.assign(x, w, want_dists=True, metric=distf)
     return labels.cpu().numpy(), dists.cpu().numpy()
 
 

@@ -3,6 +3,7 @@
 Tensors are only device-memory holders here (``data_ptr()`` goes across the ABI); every
 function launches on torch's current HIP stream and returns without synchronising.
 """
+import operator
 from typing import Optional, Tuple
 
 import numpy as np
@@ -32,24 +33,47 @@ def _codebook(w: torch.Tensor) -> torch.Tensor:
 
 
 class AssignWorkspace:
-    """Scratch for pxsom_assign, reusable across calls of the same (n_max, c, k)."""
+    """Scratch for pxsom_assign (``metric`` 2) or pxsom_assign_metric (1, 3, 4), reusable across calls of the same
+    (n_max, c, k, metric)."""
 
-    def __init__(self, n_max: int, c: int, k: int, device):
-        self.bytes = _capi.lib().pxsom_assign_workspace_bytes(int(n_max), int(c), int(k))
+    def __init__(self, n_max: int, c: int, k: int, device, metric: int = 2):
+        if metric == 2:
+            self.bytes = _capi.lib().pxsom_assign_workspace_bytes(int(n_max), int(c), int(k))
+        else:
+            self.bytes = _capi.lib().pxsom_assign_metric_workspace_bytes(int(n_max), int(c), int(k), int(metric))
         if self.bytes == 0:
-            raise _capi.PxsomError(f"unsupported assign shape n={n_max} c={c} k={k}")
-        self.n_max, self.c, self.k = int(n_max), int(c), int(k)
+            raise _capi.PxsomError(f"unsupported assign shape n={n_max} c={c} k={k} metric={metric}")
+        self.n_max, self.c, self.k, self.metric = int(n_max), int(c), int(k), int(metric)
         self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device)
 
-    def fits(self, n: int, c: int, k: int) -> bool:
-        return c == self.c and k == self.k and n <= self.n_max
+    def fits(self, n: int, c: int, k: int, metric: int = 2) -> bool:
+        return c == self.c and k == self.k and n <= self.n_max and metric == self.metric
+
+
+def _check_metric(metric: int) -> int:
+    code = None
+    if not isinstance(metric, (bool, np.bool_)):
+        try:
+            code = operator.index(metric)
+        except TypeError:
+            pass
+    if code not in _capi.METRICS:
+        raise ValueError(f"unknown metric {metric!r}: FlowSOM distf 1 (Manhattan), 2 (Euclidean), 3 (Chebyshev) "
+                         f"or 4 (cosine)")
+    return code
 
 
 def assign(x: torch.Tensor, w: torch.Tensor, labels: Optional[torch.Tensor] = None,
            dists: Optional[torch.Tensor] = None, want_dists: bool = False,
-           workspace: Optional[AssignWorkspace] = None, screen_all_lists: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+           workspace: Optional[AssignWorkspace] = None, screen_all_lists: bool = False,
+           metric: int = 2) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """BMU labels (int32, 1-based) of every row of ``x`` against codebook ``w`` [K, C] f64.  ``screen_all_lists``: every list of
-    rows for the exact path takes the long-list (screened) kernel whatever its length (PXSOM_ASSIGN_SCREEN_ALL_LISTS; same labels)."""
+    rows for the exact path takes the long-list (screened) kernel whatever its length (PXSOM_ASSIGN_SCREEN_ALL_LISTS; same labels).
+    ``metric``: FlowSOM's distf -- 2 Euclidean (pxsom_assign), 1 Manhattan, 3 Chebyshev, 4 cosine (pxsom_assign_metric, which
+    has no screen and so no lists: ``screen_all_lists`` is Euclidean-only and refused with another metric)."""
+    metric = _check_metric(metric)
+    if screen_all_lists and metric != 2:
+        raise ValueError("screen_all_lists applies to the Euclidean route only (metric 2)")
     n, c, ldx, dt = _matrix_args(x)
     w = _codebook(w)
     k = w.shape[0]
@@ -59,8 +83,15 @@ def assign(x: torch.Tensor, w: torch.Tensor, labels: Optional[torch.Tensor] = No
         labels = torch.empty(n, dtype=torch.int32, device=x.device)
     if want_dists and dists is None:
         dists = torch.empty(n, dtype=torch.float64, device=x.device)
-    if workspace is None or not workspace.fits(n, c, k):
-        workspace = AssignWorkspace(n, c, k, x.device)
+    if workspace is None or not workspace.fits(n, c, k, metric):
+        workspace = AssignWorkspace(n, c, k, x.device, metric)
+    if metric != 2:
+        rc = _capi.lib().pxsom_assign_metric(x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, labels.data_ptr(),
+                                             dists.data_ptr() if dists is not None else None,
+                                             workspace.buf.data_ptr(), workspace.bytes, metric, _capi.stream_ptr())
+        _capi.check(rc, "pxsom_assign_metric")
+        assign.last_workspace = workspace
+        return labels, dists
     rc = _capi.lib().pxsom_assign_ex(x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, labels.data_ptr(),
                                      dists.data_ptr() if dists is not None else None,
                                      workspace.buf.data_ptr(), workspace.bytes, ASSIGN_SCREEN_ALL_LISTS if screen_all_lists else 0,
@@ -361,15 +392,24 @@ ONLINE_INT_ABS = 1  # include/pxsom.h PXSOM_ONLINE_INT_ABS
 
 
 def train_online(x: torch.Tensor, w: torch.Tensor, xdim: int, ydim: int, rlen: int,
-                 alpha_range, radius_range, order: torch.Tensor, int_abs: bool = False) -> torch.Tensor:
+                 alpha_range, radius_range, order: torch.Tensor, int_abs: bool = False, metric: int = 2) -> torch.Tensor:
     """Exact online SOM (FlowSOM C_SOM) in place on ``w`` [xdim*ydim, C] f64.  ``int_abs``: the other reading of the
-    early-stop accumulator (``flowsom.RECALLED["change_abs"]``)."""
+    early-stop accumulator (``flowsom.RECALLED["change_abs"]``).  ``metric``: FlowSOM's distf of the BMU search (2 Euclidean:
+    pxsom_train_online_ex; 1 Manhattan, 3 Chebyshev, 4 cosine: pxsom_train_online_metric)."""
+    metric = _check_metric(metric)
     n, c, ldx, dt = _matrix_args(x)
     w = _codebook(w)
     if w.shape != (xdim * ydim, c):
         raise ValueError(f"codebook shape {tuple(w.shape)} != ({xdim * ydim}, {c})")
     if order.dtype != torch.int64 or not order.is_cuda or order.numel() != n * rlen:
         raise ValueError("order must be an int64 HBM vector of n*rlen row indices")
+    if metric != 2:
+        rc = _capi.lib().pxsom_train_online_metric(x.data_ptr(), n, c, ldx, dt, w.data_ptr(), int(xdim), int(ydim), int(rlen),
+                                                   float(alpha_range[0]), float(alpha_range[1]), float(radius_range[0]),
+                                                   float(radius_range[1]), order.data_ptr(), metric,
+                                                   ONLINE_INT_ABS if int_abs else 0, _capi.stream_ptr())
+        _capi.check(rc, "pxsom_train_online_metric")
+        return w
     rc = _capi.lib().pxsom_train_online_ex(x.data_ptr(), n, c, ldx, dt, w.data_ptr(), int(xdim),
                                            int(ydim), int(rlen), float(alpha_range[0]),
                                            float(alpha_range[1]), float(radius_range[0]),

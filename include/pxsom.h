@@ -426,6 +426,32 @@ int pxsom_cluster_mask(const int64_t *row_index_dev, const int64_t *column_index
 int pxsom_relabel(const int32_t *labels_dev, int64_t n, const int32_t *lut_dev, int lut_size, int32_t fill,
                   int32_t *out_dev, void *stream);
 
+/* ---- other distances: FlowSOM's `distf` codes ------------------------------------------------------------
+ * pyFlowSOM's som / map_data_to_nodes take distf = 1 (Manhattan), 2 (Euclidean), 3 (Chebyshev), 4 (cosine).  The
+ * formulas are RECALLED from FlowSOM's som.c (parity with pyFlowSOM unpinned, as for Euclidean).  All arithmetic binary64,
+ * channels j = 0..c-1 ascending, one rounding per operation:
+ *   1  d = 0; d += fabs(x_j - w_j)
+ *   3  d = 0; t = fabs(x_j - w_j); if (t > d) d = t          (a NaN channel never replaces d: an all-NaN row has d = 0)
+ *   4  nom += x_j*w_j; d1 += x_j*x_j; d2 += w_j*w_j; d = (-nom / (sqrt(d1) * sqrt(d2))) + 1   (zero row / node: NaN)
+ * pxsom_assign_metric: first strict minimum below DBL_MAX over nodes in ascending order, labels as pxsom_assign (0 when no
+ * distance compared smaller, NaN included); dist_dev (optional) gets that distance, DBL_MAX for label 0.  Every (row, node)
+ * pair is evaluated in binary64 (no screen).  Row views are not taken (PXSOM_ERR_UNSUPPORTED under one).
+ * pxsom_train_online_metric: the loop of pxsom_train_online_ex with the BMU distance replaced (nearest starts at node 0,
+ * `d[k] < d[nearest]`).  Metric 2 forwards to pxsom_assign_ex / pxsom_train_online_ex; an unknown metric is
+ * PXSOM_ERR_INVALID_ARG before any HIP call.  Workspace: pxsom_assign_metric_workspace_bytes (for metric 2 it is
+ * pxsom_assign_workspace_bytes); pxsom_assign_last_exact_rows reads n back on a metric 1 / 3 / 4 workspace. */
+#define PXSOM_METRIC_MANHATTAN 1
+#define PXSOM_METRIC_EUCLIDEAN 2
+#define PXSOM_METRIC_CHEBYSHEV 3
+#define PXSOM_METRIC_COSINE 4
+size_t pxsom_assign_metric_workspace_bytes(int64_t n, int c, int k, int metric);
+int pxsom_assign_metric(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, const double *w_dev,
+                        int k, int32_t *labels_dev, double *dist_dev, void *workspace_dev,
+                        size_t workspace_bytes, int metric, void *stream);
+int pxsom_train_online_metric(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, double *w_dev,
+                              int xdim, int ydim, int rlen, double a0, double a1, double r0, double r1,
+                              const int64_t *order_dev, int metric, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
