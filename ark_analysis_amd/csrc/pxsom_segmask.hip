@@ -1,0 +1,344 @@
+// pxsom_segmask.hip -- cell cluster masks on gfx950 (K10): border erosion + label -> value lookup over a segmentation image.
+//
+//   pxsom_segmask   find_boundaries(seg, connectivity, mode "thick" / "inner") + np.where(edges == 0, seg, 0)  (erode_mask)
+//                   then mapping.get((int32)label, unassigned) (relabel_segmentation) and the output cast
+//                   (ark/utils/data_utils.py:70-84, 204-335 of the reference)
+//
+// One fused pass.  A block is 4 waves; each wave owns a 256-column x kRowsPerWave-row tile, every lane 4 consecutive
+// pixels of a row (one 4-, 8-, 16- or 32-byte load per row, one packed store per row).  With erosion a wave loads
+// kRowsPerWave + 2 rows up front (the one-row halo above and below comes from L1 / L2: it is the neighbouring wave's or
+// block's own row, read there in the same sweep, so HBM sees each input byte about once); the left / right halo column
+// comes from the neighbouring lane by a cross-lane shuffle, and only lanes 0 and 63 load one extra element per row.
+// No LDS staging: the halo re-read is 2 of 6 rows and served by the caches, and the shuffle replaces the LDS round trip
+// (DESIGN.md K10 has the numbers).
+#include <algorithm>
+#include <cmath>
+#include <type_traits>
+
+#include "pxsom_common.h"
+
+namespace {
+
+constexpr int kWaveCols = 256;       // 64 lanes x 4 pixels
+constexpr int kRowsPerWave = 4;
+constexpr int kWaves = 4;
+constexpr int kBlockRows = kRowsPerWave * kWaves;
+constexpr int64_t kDenseMaxEntries = int64_t(1) << 24;   // 64 MB of int32 at most
+
+template <typename T>
+struct Vec4 {
+    typedef T type __attribute__((ext_vector_type(4)));
+};
+
+template <typename T>
+__device__ __forceinline__ T shfl_up1(T v)
+{
+    if constexpr (sizeof(T) == 8)
+        return (T)__shfl_up((long long)v, 1, 64);
+    else
+        return (T)__shfl_up((int)v, 1, 64);
+}
+
+template <typename T>
+__device__ __forceinline__ T shfl_down1(T v)
+{
+    if constexpr (sizeof(T) == 8)
+        return (T)__shfl_down((long long)v, 1, 64);
+    else
+        return (T)__shfl_down((int)v, 1, 64);
+}
+
+// 4 labels of row r from column c0: one wide load when the 4 lie inside the row and the rows are aligned, else element
+// loads with the column clamped to w - 1 (the clamp is scipy's reflect at distance 1: the right neighbour of the last
+// column is the column itself)
+template <typename TI>
+__device__ __forceinline__ void load_row(const TI *__restrict__ seg, int64_t ld, int r, int c0, int w, bool vec, TI (&v)[4])
+{
+    const TI *row = seg + (int64_t)r * ld;
+    if (vec && c0 + 3 < w) {
+        const typename Vec4<TI>::type x = *reinterpret_cast<const typename Vec4<TI>::type *>(row + c0);
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = x[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = row[min(c0 + k, w - 1)];
+    }
+}
+
+template <typename TV>
+struct Table {
+    const int32_t *keys;
+    const TV *values;
+    const int32_t *lut;      // dense route: index of key_min + i in keys, -1 when absent; nullptr: binary search
+    int64_t n_keys;          // < 0: no lookup
+    int32_t key_min;
+    int64_t lut_size;
+    TV unassigned;
+};
+
+template <typename TV, typename TI>
+__device__ __forceinline__ TV lookup(const Table<TV> &t, TI label)
+{
+    const int32_t key = (int32_t)(int64_t)label;            // numpy astype(np.int32): two's-complement wrap
+    int64_t idx = -1;
+    if (t.lut) {
+        const int64_t d = (int64_t)key - t.key_min;
+        if (d >= 0 && d < t.lut_size) idx = t.lut[d];
+    } else {
+        int64_t lo = 0, hi = t.n_keys;                      // first key >= `key`
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (t.keys[mid] < key) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < t.n_keys && t.keys[lo] == key) idx = lo;
+    }
+    return idx >= 0 ? t.values[idx] : t.unassigned;
+}
+
+template <typename TI, typename TO, typename TV>
+__device__ __forceinline__ TO finish(const Table<TV> &t, TI label)
+{
+    if (t.n_keys < 0) return (TO)label;   // no lookup: the (eroded) label, cast as numpy casts
+    return (TO)lookup<TV, TI>(t, label);
+}
+
+template <typename TO>
+__device__ __forceinline__ void store_row(TO *__restrict__ out, int64_t ldo, int r, int c0, int w, bool vec, const TO (&o)[4])
+{
+    TO *row = out + (int64_t)r * ldo;
+    if (vec && c0 + 3 < w) {
+        typename Vec4<TO>::type x;
+#pragma unroll
+        for (int k = 0; k < 4; k++) x[k] = o[k];
+        *reinterpret_cast<typename Vec4<TO>::type *>(row + c0) = x;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (c0 + k < w) row[c0 + k] = o[k];
+    }
+}
+
+template <typename TI, typename TO, typename TV>
+__global__ __launch_bounds__(256) void segmask_kernel(const TI *__restrict__ seg, int h, int w, int64_t ld, int erode_mode,
+                                                      int conn8, int64_t background, Table<TV> table, TO *__restrict__ out,
+                                                      int64_t ldo, bool vec_in, bool vec_out, int col_blocks)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bx = (int)(blockIdx.x % (unsigned)col_blocks), by = (int)(blockIdx.x / (unsigned)col_blocks);
+    const int row0 = by * kBlockRows + wave * kRowsPerWave;
+    if (row0 >= h) return;                                   // whole wave: the shuffles below stay inside live waves
+    const int c0 = bx * kWaveCols + lane * 4;
+    const int rows = min(kRowsPerWave, h - row0);
+
+    if (erode_mode == PXSOM_SEG_ERODE_NONE) {
+        TI v[kRowsPerWave][4];
+#pragma unroll
+        for (int i = 0; i < kRowsPerWave; i++) load_row(seg, ld, min(row0 + i, h - 1), c0, w, vec_in, v[i]);
+#pragma unroll
+        for (int i = 0; i < kRowsPerWave; i++) {
+            if (i >= rows) break;
+            TO o[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[k] = finish<TI, TO, TV>(table, v[i][k]);
+            store_row(out, ldo, row0 + i, c0, w, vec_out, o);
+        }
+        return;
+    }
+
+    // rows row0 - 1 .. row0 + kRowsPerWave, clamped into the image (reflect at distance 1), all loads in flight at once
+    constexpr int kL = kRowsPerWave + 2;
+    TI v[kL][4], left[kL], right[kL];
+#pragma unroll
+    for (int i = 0; i < kL; i++) load_row(seg, ld, min(max(row0 - 1 + i, 0), h - 1), c0, w, vec_in, v[i]);
+#pragma unroll
+    for (int i = 0; i < kL; i++) {
+        left[i] = shfl_up1(v[i][3]);     // lane - 1's last pixel
+        right[i] = shfl_down1(v[i][0]);  // lane + 1's first pixel
+    }
+    if (lane == 0 || lane == 63) {       // the halo column of the wave's tile: one element per row, from L1 / L2
+        const int cc = lane == 0 ? max(c0 - 1, 0) : min(c0 + 4, w - 1);
+#pragma unroll
+        for (int i = 0; i < kL; i++) {
+            const TI x = seg[(int64_t)min(max(row0 - 1 + i, 0), h - 1) * ld + cc];
+            if (lane == 0) left[i] = x;
+            else right[i] = x;
+        }
+    }
+#pragma unroll
+    for (int i = 1; i <= kRowsPerWave; i++) {
+        if (i > rows) break;
+        TO o[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const TI c = v[i][k];
+            const TI l0 = k == 0 ? left[i - 1] : v[i - 1][k - 1], r0 = k == 3 ? right[i - 1] : v[i - 1][k + 1];
+            const TI l1 = k == 0 ? left[i] : v[i][k - 1], r1 = k == 3 ? right[i] : v[i][k + 1];
+            const TI l2 = k == 0 ? left[i + 1] : v[i + 1][k - 1], r2 = k == 3 ? right[i + 1] : v[i + 1][k + 1];
+            bool edge = (v[i - 1][k] != c) | (v[i + 1][k] != c) | (l1 != c) | (r1 != c);
+            if (conn8) edge |= (l0 != c) | (r0 != c) | (l2 != c) | (r2 != c);
+            if (erode_mode == PXSOM_SEG_ERODE_INNER) edge &= (int64_t)c != background;
+            o[k] = finish<TI, TO, TV>(table, edge ? (TI)0 : c);
+        }
+        store_row(out, ldo, row0 + i - 1, c0, w, vec_out, o);
+    }
+}
+
+__global__ __launch_bounds__(256) void lut_scatter_kernel(const int32_t *__restrict__ keys, int64_t n, int32_t key_min,
+                                                          int64_t lut_size, int32_t *__restrict__ lut)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t d = (int64_t)keys[i] - key_min;
+        if (d >= 0 && d < lut_size) lut[d] = (int32_t)i;
+    }
+}
+
+int dtype_bytes(int dt)
+{
+    switch (dt) {
+    case PXSOM_SEG_U8: return 1;
+    case PXSOM_SEG_I16: case PXSOM_SEG_U16: return 2;
+    case PXSOM_SEG_I32: case PXSOM_SEG_U32: return 4;
+    case PXSOM_SEG_I64: case PXSOM_SEG_F64: return 8;
+    default: return 0;
+    }
+}
+
+struct Launch {
+    const void *seg;
+    int h, w;
+    int64_t ld;
+    int erode_mode, conn8;
+    int64_t background;
+    const int32_t *keys;
+    const void *values;
+    const int32_t *lut;
+    int64_t n_keys;
+    int32_t key_min;
+    int64_t lut_size;
+    double unassigned;
+    void *out;
+    int64_t ldo;
+    hipStream_t st;
+};
+
+template <typename TI, typename TO>
+int launch_typed(const Launch &a)
+{
+    typedef typename std::conditional<std::is_same<TO, double>::value, double, int32_t>::type TV;
+    Table<TV> t;
+    t.keys = a.keys;
+    t.values = reinterpret_cast<const TV *>(a.values);
+    t.lut = a.lut;
+    t.n_keys = a.n_keys;
+    t.key_min = a.key_min;
+    t.lut_size = a.lut_size;
+    t.unassigned = (TV)a.unassigned;
+    const auto aligned = [](const void *p, int64_t stride, size_t vbytes) {
+        return (reinterpret_cast<uintptr_t>(p) % vbytes) == 0 && stride % 4 == 0;
+    };
+    const bool vec_in = aligned(a.seg, a.ld, 4 * sizeof(TI)), vec_out = aligned(a.out, a.ldo, 4 * sizeof(TO));
+    const int col_blocks = (a.w + kWaveCols - 1) / kWaveCols;
+    const int64_t blocks = (int64_t)col_blocks * ((a.h + kBlockRows - 1) / kBlockRows);
+    if (blocks > 0x7fffffff) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_segmask: image too large");
+    PXSOM_TIMED_LAUNCH((segmask_kernel<TI, TO, TV>), dim3((unsigned)blocks), dim3(256), 0, a.st,
+                       reinterpret_cast<const TI *>(a.seg), a.h, a.w, a.ld, a.erode_mode, a.conn8, a.background, t,
+                       reinterpret_cast<TO *>(a.out), a.ldo, vec_in, vec_out, col_blocks);
+    PXSOM_LAUNCH_CHECK("segmask_kernel");
+    return PXSOM_OK;
+}
+
+template <typename TI>
+int launch_in(const Launch &a, int out_dtype, int seg_dtype)
+{
+    if (out_dtype == seg_dtype) return launch_typed<TI, TI>(a);
+    if (out_dtype == PXSOM_SEG_I16) return launch_typed<TI, int16_t>(a);
+    if (out_dtype == PXSOM_SEG_I32) return launch_typed<TI, int32_t>(a);
+    return launch_typed<TI, double>(a);
+}
+
+}  // namespace
+
+PXSOM_EXPORT size_t pxsom_segmask_workspace_bytes(int64_t n_keys, int32_t key_min, int32_t key_max)
+{
+    if (n_keys <= 0 || key_max < key_min) return 0;
+    const int64_t range = (int64_t)key_max - key_min + 1;
+    // dense when the LUT is at most 64 MB and not far sparser than the table (16 slots a key + 64 Ki)
+    if (range > kDenseMaxEntries || range > 16 * n_keys + 65536) return 0;
+    return (size_t)range * sizeof(int32_t);
+}
+
+PXSOM_EXPORT int pxsom_segmask(const void *seg_dev, int seg_dtype, int h, int w, int64_t ld, int erode_mode,
+                               int connectivity, int64_t background, const int32_t *keys_dev, const void *values_dev,
+                               int64_t n_keys, int32_t key_min, int32_t key_max, double unassigned, void *out_dev,
+                               int out_dtype, int64_t ldo, void *workspace_dev, size_t workspace_bytes, int flags,
+                               void *stream)
+{
+    const char *fn = "pxsom_segmask";
+    if (seg_dtype < PXSOM_SEG_U8 || seg_dtype > PXSOM_SEG_I64)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad seg_dtype %d", fn, seg_dtype);
+    if (out_dtype != seg_dtype && out_dtype != PXSOM_SEG_I16 && out_dtype != PXSOM_SEG_I32 && out_dtype != PXSOM_SEG_F64)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad out_dtype %d", fn, out_dtype);
+    if (erode_mode < PXSOM_SEG_ERODE_NONE || erode_mode > PXSOM_SEG_ERODE_INNER)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad erode_mode %d", fn, erode_mode);
+    if (erode_mode != PXSOM_SEG_ERODE_NONE && connectivity < 1)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: connectivity %d < 1", fn, connectivity);
+    if (h < 1 || w < 1 || ld < w || ldo < w)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad sizes (%d x %d, ld %lld, ldo %lld)", fn, h, w, (long long)ld,
+                           (long long)ldo);
+    if (flags & ~PXSOM_SEGMASK_FORCE_SEARCH) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: unknown flags %d", fn, flags);
+    if (!seg_dev || !out_dev) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: null image", fn);
+    if (n_keys > 0 && (!keys_dev || !values_dev || key_min > key_max))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad table (null, or key_min > key_max)", fn);
+    if (n_keys >= 0 && out_dtype != PXSOM_SEG_F64 &&
+        !(std::isfinite(unassigned) && unassigned == std::floor(unassigned) && unassigned >= -2147483648.0 &&
+          unassigned <= 2147483647.0))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: unassigned %g is not an int32 value", fn, unassigned);
+    if (erode_mode != PXSOM_SEG_ERODE_NONE) {   // erosion reads neighbours another block may already have written
+        const char *s0 = static_cast<const char *>(seg_dev), *o0 = static_cast<const char *>(out_dev);
+        const char *s1 = s0 + ((int64_t)(h - 1) * ld + w) * dtype_bytes(seg_dtype);
+        const char *o1 = o0 + ((int64_t)(h - 1) * ldo + w) * dtype_bytes(out_dtype);
+        if (s0 < o1 && o0 < s1) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps seg under erosion", fn);
+    }
+    const size_t need = n_keys > 0 && !(flags & PXSOM_SEGMASK_FORCE_SEARCH)
+                            ? pxsom_segmask_workspace_bytes(n_keys, key_min, key_max) : 0;
+    if (need > 0 && (!workspace_dev || workspace_bytes < need))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
+
+    Launch a;
+    a.seg = seg_dev;
+    a.h = h;
+    a.w = w;
+    a.ld = ld;
+    a.erode_mode = erode_mode;
+    a.conn8 = connectivity >= 2;
+    a.background = background;
+    a.keys = keys_dev;
+    a.values = values_dev;
+    a.lut = nullptr;
+    a.n_keys = n_keys < 0 ? -1 : n_keys;
+    a.key_min = key_min;
+    a.lut_size = 0;
+    a.unassigned = unassigned;
+    a.out = out_dev;
+    a.ldo = ldo;
+    a.st = reinterpret_cast<hipStream_t>(stream);
+    if (need > 0) {
+        int32_t *lut = static_cast<int32_t *>(workspace_dev);
+        a.lut = lut;
+        a.lut_size = (int64_t)key_max - key_min + 1;
+        PXSOM_HIP_TRY(hipMemsetAsync(lut, 0xFF, need, a.st));   // every slot -1: absent
+        const int64_t grid = std::min<int64_t>((n_keys + 255) / 256, (int64_t)pxsom::device_cu_count() * 4);
+        hipLaunchKernelGGL(lut_scatter_kernel, dim3((unsigned)grid), dim3(256), 0, a.st, keys_dev, n_keys, key_min,
+                           a.lut_size, lut);
+        PXSOM_LAUNCH_CHECK("lut_scatter_kernel");
+    }
+    switch (seg_dtype) {
+    case PXSOM_SEG_U8: return launch_in<uint8_t>(a, out_dtype, seg_dtype);
+    case PXSOM_SEG_I16: return launch_in<int16_t>(a, out_dtype, seg_dtype);
+    case PXSOM_SEG_U16: return launch_in<uint16_t>(a, out_dtype, seg_dtype);
+    case PXSOM_SEG_I32: return launch_in<int32_t>(a, out_dtype, seg_dtype);
+    case PXSOM_SEG_U32: return launch_in<uint32_t>(a, out_dtype, seg_dtype);
+    default: return launch_in<int64_t>(a, out_dtype, seg_dtype);
+    }
+}

@@ -603,6 +603,75 @@ def relabel(labels: torch.Tensor, lut: torch.Tensor, fill: int = -1, out: Option
     return out
 
 
+# include/pxsom.h PXSOM_SEG_*: the label dtypes of a segmentation image, and float64 (an output only)
+SEG_DTYPES = {torch.uint8: 0, torch.int16: 1, torch.uint16: 2, torch.int32: 3, torch.uint32: 4, torch.int64: 5}
+SEG_F64 = 6
+SEG_ERODE = {None: 0, "thick": 1, "inner": 2}
+SEGMASK_FORCE_SEARCH = 1
+
+
+def segmask_table(keys, values, device, float_values: bool = False):
+    """Host (key -> value) arrays as the device table of :func:`segmentation_mask`: ``keys`` int32, sorted ascending and
+    unique (checked here: the library relies on it), ``values`` int32, or float64 with ``float_values``."""
+    keys = np.ascontiguousarray(keys, dtype=np.int32)
+    values = np.ascontiguousarray(values, dtype=np.float64 if float_values else np.int32)
+    if keys.ndim != 1 or values.shape != keys.shape:
+        raise ValueError("keys and values must be vectors of one length")
+    if keys.size > 1 and not np.all(keys[1:] > keys[:-1]):
+        raise ValueError("keys must be sorted ascending without duplicates")
+    return (torch.from_numpy(keys).to(device), torch.from_numpy(values).to(device),
+            int(keys[0]) if keys.size else 0, int(keys[-1]) if keys.size else 0)
+
+
+def segmentation_mask(seg: torch.Tensor, erode: Optional[str] = None, connectivity: int = 1, background: int = 0,
+                      table=None, unassigned=0, out_dtype: Optional[torch.dtype] = None, force_search: bool = False,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pass of pxsom_segmask over a ``[H, W]`` label image in HBM (rows contiguous, any row stride): optional border
+    erosion (``erode`` "thick" / "inner": skimage's find_boundaries with ``connectivity`` and ``background``; boundary
+    pixels become 0), then the optional lookup ``table`` of :func:`segmask_table` (label cast to int32, ``unassigned``
+    where the table has no entry), stored as ``out_dtype`` (int16, int32, float64 or the image's dtype; default: the
+    image's).  ``force_search`` takes the binary-search route even where a dense LUT would fit."""
+    if seg.dim() != 2 or not seg.is_cuda or seg.dtype not in SEG_DTYPES:
+        raise ValueError("seg must be a 2-D uint8 / int16 / uint16 / int32 / uint32 / int64 HBM tensor")
+    h, w = seg.shape
+    if h == 0 or w == 0:
+        raise ValueError("seg must not be empty")
+    if w > 1 and seg.stride(1) != 1:
+        raise ValueError("seg rows must be contiguous (stride(1) == 1)")
+    if erode not in SEG_ERODE:
+        raise NotImplementedError(f"erosion mode {erode!r}: only 'thick' and 'inner' are implemented")
+    connectivity = max(int(connectivity), 1)        # scipy's generate_binary_structure treats < 1 as 1
+    if out_dtype is None:
+        out_dtype = seg.dtype
+    if out_dtype != seg.dtype and out_dtype not in (torch.int16, torch.int32, torch.float64):
+        raise ValueError("out_dtype must be int16, int32, float64 or the image's dtype")
+    code_out = SEG_F64 if out_dtype == torch.float64 else SEG_DTYPES[out_dtype]
+    if out is None:
+        out = torch.empty((h, w), dtype=out_dtype, device=seg.device)
+    elif out.shape != (h, w) or out.dtype != out_dtype or not out.is_cuda or (w > 1 and out.stride(1) != 1):
+        raise ValueError("out must be a [H, W] HBM tensor of out_dtype with contiguous rows")
+    ld = seg.stride(0) if h > 1 else w
+    ldo = out.stride(0) if h > 1 else w
+    lib = _capi.lib()
+    if table is None:
+        keys = values = None
+        n_keys, kmin, kmax = -1, 0, 0
+    else:
+        keys, values, kmin, kmax = table
+        n_keys = keys.numel()
+        if values.dtype != (torch.float64 if out_dtype == torch.float64 else torch.int32):
+            raise ValueError("table values must be float64 for a float64 output, int32 otherwise")
+    wsb = 0 if force_search or n_keys <= 0 else lib.pxsom_segmask_workspace_bytes(n_keys, kmin, kmax)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=seg.device) if wsb else None
+    rc = lib.pxsom_segmask(seg.data_ptr(), SEG_DTYPES[seg.dtype], h, w, ld, SEG_ERODE[erode], connectivity, int(background),
+                           keys.data_ptr() if keys is not None else None, values.data_ptr() if values is not None else None,
+                           n_keys, kmin, kmax, float(unassigned), out.data_ptr(), code_out, ldo,
+                           ws.data_ptr() if ws is not None else None, wsb,
+                           SEGMASK_FORCE_SEARCH if force_search else 0, _capi.stream_ptr())
+    _capi.check(rc, "pxsom_segmask")
+    return out
+
+
 class AssignSumsWorkspace:
     """Scratch for pxsom_assign_sums, reusable across calls of the same (n_max, c, k)."""
 

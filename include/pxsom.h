@@ -452,6 +452,43 @@ int pxsom_train_online_metric(const void *x_dev, int64_t n, int c, int64_t ldx, 
                               int xdim, int ydim, int rlen, double a0, double a1, double r0, double r1,
                               const int64_t *order_dev, int metric, int flags, void *stream);
 
+/* ---- cell cluster masks: border erosion + label lookup over a segmentation image (K10) ----------------------
+ * reference: ark/utils/data_utils.py erode_mask (skimage.segmentation.find_boundaries, then np.where(edges == 0, seg, 0)),
+ * relabel_segmentation / label_cells_by_cluster / map_segmentation_labels.  One stream-ordered pass over seg_dev [h, w]
+ * (row stride ld elements, ld >= w) of seg_dtype (PXSOM_SEG_U8 .. PXSOM_SEG_I64); per pixel:
+ *   1. erosion (erode_mode != PXSOM_SEG_ERODE_NONE): the pixel is a boundary pixel when an in-image neighbour holds a
+ *      different label (4-neighbourhood for connectivity 1, 8-neighbourhood for connectivity >= 2; a neighbour outside the
+ *      image counts as equal: scipy's reflect border of dilation != erosion).  PXSOM_SEG_ERODE_INNER also requires
+ *      label != background (compared as int64).  Labels are compared in seg_dtype.  A boundary pixel becomes 0.
+ *   2. lookup (n_keys >= 0): key = (int32)label (two's-complement wrap, numpy's astype(np.int32)); the pixel gets
+ *      values_dev[i] where keys_dev[i] == key, else `unassigned`.  n_keys < 0: no lookup, the (eroded) label itself is stored.
+ *   3. store in out_dtype (PXSOM_SEG_I16 / PXSOM_SEG_I32 / PXSOM_SEG_F64, or seg_dtype itself): integer stores wrap as
+ *      numpy's astype does; out_dev [h, w] with row stride ldo >= w.
+ * values_dev is double [n_keys] for PXSOM_SEG_F64 output, int32 [n_keys] otherwise; `unassigned` is converted the same
+ * way (it must be an int32 value for integer outputs).  keys_dev [n_keys] int32 MUST be sorted ascending without
+ * duplicates, with key_min = keys[0] and key_max = keys[n_keys - 1]: the library does not check this (the Python wrapper
+ * does).  Table route: a dense index LUT over [key_min, key_max] built in the workspace when
+ * pxsom_segmask_workspace_bytes(n_keys, key_min, key_max) > 0 (and PXSOM_SEGMASK_FORCE_SEARCH is not set), else a binary
+ * search over keys_dev; both give identical results.  Bad dtype / mode / connectivity / sizes / strides / workspace:
+ * PXSOM_ERR_INVALID_ARG before any HIP call.  In-place (out_dev == seg_dev) is allowed when out and seg share dtype and
+ * stride and there is no erosion. */
+#define PXSOM_SEG_U8 0
+#define PXSOM_SEG_I16 1
+#define PXSOM_SEG_U16 2
+#define PXSOM_SEG_I32 3
+#define PXSOM_SEG_U32 4
+#define PXSOM_SEG_I64 5
+#define PXSOM_SEG_F64 6      /* output only */
+#define PXSOM_SEG_ERODE_NONE 0
+#define PXSOM_SEG_ERODE_THICK 1
+#define PXSOM_SEG_ERODE_INNER 2
+#define PXSOM_SEGMASK_FORCE_SEARCH 1
+size_t pxsom_segmask_workspace_bytes(int64_t n_keys, int32_t key_min, int32_t key_max);
+int pxsom_segmask(const void *seg_dev, int seg_dtype, int h, int w, int64_t ld, int erode_mode, int connectivity,
+                  int64_t background, const int32_t *keys_dev, const void *values_dev, int64_t n_keys, int32_t key_min,
+                  int32_t key_max, double unassigned, void *out_dev, int out_dtype, int64_t ldo, void *workspace_dev,
+                  size_t workspace_bytes, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,179 @@
+"""pxsom_segmask on the GPU (erosion + label lookup of the cell cluster masks), array_equal against the numpy statement of
+tests/cell_mask_reference.py, and the drop-in functions of ark_analysis_amd.utils.data_utils on the HIP path against the
+g15 fixtures of the reference."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import cell_mask_reference as cr
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = {"u8": (np.uint8, torch.uint8), "i16": (np.int16, torch.int16), "u16": (np.uint16, torch.uint16),
+          "i32": (np.int32, torch.int32), "u32": (np.uint32, torch.uint32), "i64": (np.int64, torch.int64)}
+EROSIONS = [(None, 1), ("thick", 1), ("thick", 2), ("inner", 1), ("inner", 2)]
+OUTS = {"i16": (np.int16, torch.int16), "i32": (np.int32, torch.int32), "f64": (np.float64, torch.float64)}
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _labels(rs, h, w, npdt, n=9):
+    """Rectangular cells of labels spread over the dtype's range (wrapping to negative int32 for uint32 / int64)."""
+    info = np.iinfo(npdt)
+    pool = np.unique(np.concatenate([[0, 1, 2, info.max, info.max - 1],
+                                     rs.randint(0, min(info.max, 2 ** 62), size=40, dtype=np.int64)]))
+    if info.min < 0:
+        pool = np.concatenate([pool, [info.min, -5, -1]])
+    ny, nx = min(n, h), min(n, w)
+    ry = np.sort(rs.randint(0, ny, size=h))
+    rx = np.sort(rs.randint(0, nx, size=w))
+    ids = rs.choice(pool, size=(ny, nx))
+    img = ids[ry[:, None], rx[None, :]]
+    img[rs.rand(h, w) < 0.03] = rs.choice(pool)        # single-pixel cells
+    return img.astype(npdt)
+
+
+def _table_for(rs, seg, n_extra=5, float_values=False, big_key=False):
+    labels = np.unique(seg.astype(np.int32))
+    keys = labels[rs.rand(labels.size) < 0.8]
+    keys = np.unique(np.concatenate([keys, rs.randint(-1000, 1000, size=n_extra)]).astype(np.int32))
+    if big_key:
+        keys = np.unique(np.concatenate([keys, [2 ** 31 - 1]]).astype(np.int32))
+    values = rs.randn(keys.size) * 1e3 if float_values else rs.randint(-70000, 70000, size=keys.size)
+    return keys, values
+
+
+def _device(gpu, seg, erode=None, conn=1, background=0, keys=None, values=None, unassigned=0, out=None, pad=0,
+            force_search=False, offset=0):
+    from ark_analysis_amd import som_device
+    npdt = seg.dtype
+    tdt = {np.dtype(v[0]): v[1] for v in DTYPES.values()}[npdt]
+    h, w = seg.shape
+    if pad or offset:
+        wide = torch.zeros((h, w + pad + offset), dtype=tdt, device=gpu)
+        wide[:, offset:offset + w] = torch.from_numpy(seg).to(gpu)
+        t = wide[:, offset:offset + w]
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(seg)).to(gpu)
+    out_t = {None: None, **{np.dtype(v[0]): v[1] for v in OUTS.values()}}.get(None if out is None else np.dtype(out), tdt)
+    table = None
+    if keys is not None:
+        table = som_device.segmask_table(keys, values, gpu, float_values=out_t == torch.float64)
+    res = som_device.segmentation_mask(t, erode=erode, connectivity=conn, background=background, table=table,
+                                       unassigned=unassigned, out_dtype=out_t, force_search=force_search)
+    torch.cuda.synchronize()
+    return res.cpu().numpy()
+
+
+def _check(gpu, seg, erode=None, conn=1, background=0, keys=None, values=None, unassigned=0, out=None, **kw):
+    got = _device(gpu, seg, erode, conn, background, keys, values, unassigned, out, **kw)
+    want = cr.segmask(seg, erode, conn, background, keys, values, unassigned, out)
+    assert got.dtype == want.dtype and got.shape == want.shape
+    assert np.array_equal(got, want), (seg.dtype, erode, conn, out, int((got != want).sum()))
+
+
+@pytest.mark.parametrize("dt", list(DTYPES))
+def test_every_dtype_erosion_and_output(gpu, dt):
+    rs = np.random.RandomState(7)
+    npdt = DTYPES[dt][0]
+    seg = _labels(rs, 37, 45, npdt)
+    bg = int(seg[5, 5])
+    keys, values = _table_for(rs, seg)
+    fkeys, fvalues = _table_for(rs, seg, float_values=True)
+    for erode, conn in EROSIONS:
+        _check(gpu, seg, erode, conn, bg)                                   # erode_mask alone: the input dtype
+        for out in OUTS:
+            _check(gpu, seg, erode, conn, 0, out=OUTS[out][0])              # no lookup, cast
+            if out == "f64":
+                _check(gpu, seg, erode, conn, bg, fkeys, fvalues, -0.5, np.float64)
+            else:
+                _check(gpu, seg, erode, conn, bg, keys, values, 40000, OUTS[out][0])
+        _check(gpu, seg, erode, conn, 0, keys, values, -3, npdt)            # lookup into the input dtype
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 7), (1, 1030), (9, 1), (1025, 1), (17, 33), (300, 517), (33, 260)])
+def test_shapes(gpu, shape):
+    rs = np.random.RandomState(sum(shape))
+    for dt in ("u8", "i32", "i64"):
+        seg = _labels(rs, *shape, DTYPES[dt][0], n=5)
+        keys, values = _table_for(rs, seg)
+        for erode, conn in EROSIONS:
+            _check(gpu, seg, erode, conn, 0, keys, values, 9, np.int16)
+            _check(gpu, seg, erode, conn)
+
+
+def test_row_stride_and_unaligned_rows(gpu):
+    rs = np.random.RandomState(3)
+    for dt in DTYPES:
+        seg = _labels(rs, 41, 70, DTYPES[dt][0])
+        keys, values = _table_for(rs, seg)
+        for pad, offset in ((6, 0), (3, 0), (0, 1), (5, 3)):
+            _check(gpu, seg, "thick", 2, 0, keys, values, 1, np.int16, pad=pad, offset=offset)
+            _check(gpu, seg, "inner", 1, 0, pad=pad, offset=offset)
+
+
+def test_dense_and_search_routes_agree(gpu):
+    from ark_analysis_amd import _capi
+    rs = np.random.RandomState(11)
+    ids = rs.randint(0, 3000, size=(40, 40))                              # labels of a compact range: a LUT fits
+    seg = ids[np.sort(rs.randint(0, 40, 130))[:, None], np.sort(rs.randint(0, 40, 250))[None, :]].astype(np.int32)
+    keys, values = _table_for(rs, seg)
+    assert _capi.lib().pxsom_segmask_workspace_bytes(keys.size, int(keys[0]), int(keys[-1])) > 0
+    dense = _device(gpu, seg, "thick", 2, 0, keys, values, 5, np.int16)
+    search = _device(gpu, seg, "thick", 2, 0, keys, values, 5, np.int16, force_search=True)
+    assert np.array_equal(dense, search)
+    _check(gpu, seg, "thick", 2, 0, keys, values, 5, np.int16, force_search=True)
+    # a key of 2^31 - 1 makes the range too sparse for a LUT: the automatic route searches
+    bkeys, bvalues = _table_for(rs, seg, big_key=True)
+    assert _capi.lib().pxsom_segmask_workspace_bytes(bkeys.size, int(bkeys[0]), int(bkeys[-1])) == 0
+    _check(gpu, seg, None, 1, 0, bkeys, bvalues, 5, np.int32)
+    fk, fv = _table_for(rs, seg, float_values=True)
+    assert np.array_equal(_device(gpu, seg, None, 1, 0, fk, fv, np.nan, np.float64),
+                          _device(gpu, seg, None, 1, 0, fk, fv, np.nan, np.float64, force_search=True), equal_nan=True)
+
+
+def test_wrapped_labels_and_empty_table(gpu):
+    seg64 = np.array([[2 ** 32 - 1, 2 ** 32 + 5, -7, 3], [2 ** 40 + 3, 0, -(2 ** 33) - 1, 3]], dtype=np.int64)
+    seg32 = np.array([[4294967295, 4294967290, 5, 2 ** 31]], dtype=np.uint32)
+    keys, values = np.array([-2 ** 31, -7, -6, -1, 3, 5], dtype=np.int32), np.array([1, 2, 3, 4, 5, 6])
+    for seg in (seg64, seg32):
+        for force in (False, True):
+            _check(gpu, seg, None, 1, 0, keys, values, 99, np.int32, force_search=force)
+            _check(gpu, seg, "thick", 2, 0, keys, values, 99, np.int16, force_search=force)
+        _check(gpu, seg, None, 1, 0, np.zeros(0, np.int32), np.zeros(0), 42, np.int16)      # empty table
+        _check(gpu, seg, None, 1, 0, np.zeros(0, np.int32), np.zeros(0), 2.5, np.float64)
+
+
+@pytest.mark.parametrize("n", [1024, 2048])
+def test_voronoi_fov(gpu, n):
+    seg = cr.voronoi_labels(n, n, 20000, seed=n)
+    rs = np.random.RandomState(n)
+    keys, values = _table_for(rs, seg)
+    keys = np.unique(np.concatenate([[0], keys])).astype(np.int32)
+    values = rs.randint(1, 40, size=keys.size)
+    values[keys == 0] = 0
+    _check(gpu, seg, "thick", 2, 0, keys, values, 41, np.int16)
+    _check(gpu, seg, "thick", 2, 0, keys, values, 41, np.int16, force_search=True)
+    _check(gpu, seg, None, 1, 0, keys, rs.rand(keys.size), 0.0, np.float64)
+    _check(gpu, seg, "inner", 1, 0)
+
+
+def test_dropins_on_the_hip_path(gpu, tmp_path):
+    import pandas as pd
+    from ark_analysis_amd.utils import data_utils as du
+    from tests import test_cell_cluster_masks as cpu
+    g = np.load(os.path.join(GOLD, "g15_erode.npz"))
+    assert np.array_equal(du.erode_mask(g["seg"][..., None], connectivity=2, mode="thick", background=0),
+                          g["c2_thick_hw1"])
+    assert np.array_equal(du.erode_mask(g["seg"], connectivity=2, mode="inner", background=7), g["c2_inner_bg7"])
+    g = np.load(os.path.join(GOLD, "g15_label_cells.npz"))
+    wide = pd.DataFrame({"fov": "fovw", "label": g["wide_label"], "k": g["wide_cluster"]})
+    got = du.label_cells_by_cluster("fovw", du.ClusterMaskData(wide, "fov", "label", "k"), g["wide_seg"])
+    assert got.dtype == np.int16 and np.array_equal(got, g["wide_mask"])
+    g = np.load(os.path.join(GOLD, "g15_map_values.npz"))
+    got = du.map_segmentation_labels(pd.Series(g["labels"]), pd.Series(g["values"]), g["seg"])
+    assert got.dtype == np.float64 and np.array_equal(got, g["series"])
+    g = np.load(os.path.join(GOLD, "g15_saved_masks.npz"))
+    cpu.run_saved_masks(du, str(tmp_path), g)
+    cpu._check_saved(str(tmp_path), g)
