@@ -1700,13 +1700,14 @@ PXSOM_EXPORT int pxsom_assign_sums_ex(const void *x_dev, int64_t n, int c, int64
     const size_t need = pxsom_assign_sums_workspace_bytes(n, c, k);
     if (!workspace_dev || workspace_bytes < need)
         return pxsom::fail(PXSOM_ERR_WORKSPACE, "pxsom_assign_sums: workspace %zu < %zu bytes", workspace_bytes, need);
-    if (n == 0) return PXSOM_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t scratch_bytes = pxsom_assign_sums_scratch_bytes(c, k), stats_bytes = scratch_bytes - 256;
     double *scratch = reinterpret_cast<double *>(workspace_dev);
     void *assign_dev = reinterpret_cast<char *>(workspace_dev) + scratch_bytes;
     const size_t assign_ws = workspace_bytes - scratch_bytes;
+    // cleared ahead of the empty case too: a caller may pass the flag again after any successful call, an empty one included
     if (!(flags & PXSOM_TABLES_SCRATCH_CLEAN)) PXSOM_HIP_TRY(hipMemsetAsync(scratch, 0, scratch_bytes, st));   // statistics + ticket
+    if (n == 0) return PXSOM_OK;
     bool fused = false;
     pxsom_bmu::FinishTables fin;
     fin.sums = sums_dev;

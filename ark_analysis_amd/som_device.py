@@ -713,7 +713,9 @@ def assign_sums(x: torch.Tensor, w: torch.Tensor, labels: Optional[torch.Tensor]
     rc = _capi.lib().pxsom_assign_sums_ex(x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, labels.data_ptr(), sums.data_ptr(),
                                           counts.data_ptr(), workspace.buf.data_ptr(), workspace.bytes, flags, _capi.stream_ptr())
     _capi.check(rc, "pxsom_assign_sums_ex")
-    workspace.clean = True
+    # vouched for again only after a call that ran over rows (which leaves the region zero) or cleared the region itself (no
+    # flag); an empty call with the flag touches nothing, and the next call clears once more
+    workspace.clean = n > 0 or not flags
     return labels, sums, counts
 
 
@@ -731,4 +733,4 @@ def assign_means(x: torch.Tensor, w: torch.Tensor, labels: torch.Tensor, sums: t
                                            counts.data_ptr(), means.data_ptr() if means is not None else None,
                                            workspace.buf.data_ptr(), workspace.bytes, flags, _capi.stream_ptr())
     _capi.check(rc, "pxsom_assign_means_ex")
-    workspace.clean = True
+    workspace.clean = n > 0 or not flags   # as assign_sums

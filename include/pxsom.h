@@ -257,7 +257,9 @@ int pxsom_batch_train_finish(const double *wbuf_dev, const double *stats_ring_de
  * (results stay exact -- every label is settled against the binary64 codebook -- but most rows would be listed).
  * Oracle of record: oracle/pxsom_oracle.c orc_som_batch_sched.  Reference call replaced: cluster_helpers.py:98-116. */
 /* Reproducible statistics for binary64 rows (sum_quantum > 0; ignored for binary32 / binary16 rows).  The per-BMU sums
- * of a step are floating-point additions in whatever order the workgroups and ranks deliver them; for binary64 rows that
+ * of a step are floating-point additions in whatever order the workgroups and ranks deliver them.  binary32 / binary16 rows
+ * whose partial sums all fit binary64's 53 bits (counts-like data, binary16 values) give exact, order-free sums; wider
+ * ranges (values far below the sums they join) can round a sum in its last bit.  For binary64 rows that
  * order leaves 1e-16 noise which the degenerate first steps of a pass (near-identical nodes) can amplify into different
  * BMUs -- two runs on the same data then end in different codebooks, where the reference pins same-seed retraining
  * (tests/phenotyping/cluster_helpers_test.py:323-332 of the reference).  With sum_quantum = q (a power of two) every
