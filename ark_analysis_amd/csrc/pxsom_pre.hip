@@ -2,6 +2,9 @@
 //
 //   pxsom_gaussian_blur_hwc        scipy.ndimage.gaussian_filter(plane, sigma) per channel
 //                                  (/root/reference/src/ark/phenotyping/pixie_preprocessing.py:47-49)
+//   pxsom_gaussian_blur_plane      the same on one [h, w] plane in its own dtype (smooth_channels,
+//                                  pixel_cluster_utils.py:183-230)
+//   pxsom_zero_by_seg              img[seg > 0] = 0 / img[seg == 0] = 0 (filter_with_nuclear_mask, :233-291)
 //   pxsom_rowsum_filter_normalize  row-sum threshold + non-zero filter + row normalisation + compaction
 //                                  (pixie_preprocessing.py:67-75, pixel_cluster_utils.py:126-130)
 //   pxsom_normalize_columns        x[:, j] / norm[j]  (cluster_helpers.py:242-246)
@@ -42,15 +45,33 @@ __device__ __forceinline__ int reflect_idx(int i, int len)
     return m < len ? m : sz2 - 1 - m;
 }
 
+// How a blur pass stores its binary64 sums: scipy's correlate1d writes each output line into the output array, i.e. in
+// that array's dtype, and the second pass reads the first pass's output from there.
+//   StoreF64      binary64 image
+//   StoreF64R32   the image holds float32 values (widened): each pass rounds its output to float32
+//   StoreAs<T>    a plane in its own dtype T: float rounds to nearest, integers truncate toward zero (a C cast)
+struct StoreF64 {
+    using E = double;
+    static __device__ __forceinline__ E put(double v) { return v; }
+};
+struct StoreF64R32 {
+    using E = double;
+    static __device__ __forceinline__ E put(double v) { return (double)(float)v; }
+};
+template <typename T>
+struct StoreAs {
+    using E = T;
+    static __device__ __forceinline__ E put(double v) { return (T)v; }
+};
+
 // One pass of scipy's correlate1d, symmetric-kernel branch:
 //   tmp = in[0]*w[0];  for d = r .. 1:  tmp += (in[-d] + in[+d]) * w[d]
+// in binary64 (every stored value widens exactly), result stored through S.
 // AXIS 0: along image rows (stride W*C), AXIS 1: along image columns (stride C).
-// R32: the image holds float32 values (widened): scipy then computes each line in binary64 but stores the pass's
-// result as float32, so each pass rounds its output to float32.
 //
 // Generic form (any radius, tiny images): thread <-> one output element, every tap a coalesced read served by L1 / L2.
-template <int AXIS, bool R32>
-__global__ __launch_bounds__(256) void blur_pass_kernel(const double *__restrict__ in, double *__restrict__ out,
+template <int AXIS, typename S>
+__global__ __launch_bounds__(256) void blur_pass_kernel(const typename S::E *__restrict__ in, typename S::E *__restrict__ out,
                                                         int H, int W, int C, Taps taps)
 {
     const int64_t total = (int64_t)H * W * C;
@@ -62,14 +83,14 @@ __global__ __launch_bounds__(256) void blur_pass_kernel(const double *__restrict
         const int pos = AXIS == 0 ? y : xcol, len = AXIS == 0 ? H : W;
         const int64_t stride = AXIS == 0 ? wc : C;
         const int64_t base = e - (int64_t)pos * stride;
-        double tmp = in[e] * taps.w[0];
+        double tmp = (double)in[e] * taps.w[0];
         const bool interior = pos >= taps.radius && pos + taps.radius < len;
         for (int d = taps.radius; d >= 1; d--) {
             const int lo = interior ? pos - d : reflect_idx(pos - d, len);
             const int hi = interior ? pos + d : reflect_idx(pos + d, len);
-            tmp += (in[base + (int64_t)lo * stride] + in[base + (int64_t)hi * stride]) * taps.w[d];
+            tmp += ((double)in[base + (int64_t)lo * stride] + (double)in[base + (int64_t)hi * stride]) * taps.w[d];
         }
-        out[e] = R32 ? (double)(float)tmp : tmp;
+        out[e] = S::put(tmp);
     }
 }
 
@@ -640,13 +661,105 @@ PXSOM_EXPORT int pxsom_gaussian_blur_hwc(double *img_dev, double *tmp_dev, int h
     }
     const int grid = (int)std::min<int64_t>((total + 255) / 256, (int64_t)pxsom::device_cu_count() * 16);
     if (f32_semantics) {
-        hipLaunchKernelGGL((blur_pass_kernel<0, true>), dim3(grid), dim3(256), 0, st, img_dev, tmp_dev, h, w, c, taps);
-        hipLaunchKernelGGL((blur_pass_kernel<1, true>), dim3(grid), dim3(256), 0, st, tmp_dev, img_dev, h, w, c, taps);
+        hipLaunchKernelGGL((blur_pass_kernel<0, StoreF64R32>), dim3(grid), dim3(256), 0, st, img_dev, tmp_dev, h, w, c, taps);
+        hipLaunchKernelGGL((blur_pass_kernel<1, StoreF64R32>), dim3(grid), dim3(256), 0, st, tmp_dev, img_dev, h, w, c, taps);
     } else {
-        hipLaunchKernelGGL((blur_pass_kernel<0, false>), dim3(grid), dim3(256), 0, st, img_dev, tmp_dev, h, w, c, taps);
-        hipLaunchKernelGGL((blur_pass_kernel<1, false>), dim3(grid), dim3(256), 0, st, tmp_dev, img_dev, h, w, c, taps);
+        hipLaunchKernelGGL((blur_pass_kernel<0, StoreF64>), dim3(grid), dim3(256), 0, st, img_dev, tmp_dev, h, w, c, taps);
+        hipLaunchKernelGGL((blur_pass_kernel<1, StoreF64>), dim3(grid), dim3(256), 0, st, tmp_dev, img_dev, h, w, c, taps);
     }
     PXSOM_LAUNCH_CHECK("blur_pass_kernel");
+    return PXSOM_OK;
+}
+
+namespace {
+template <typename T>
+void launch_plane_blur(const void *in, void *out, void *tmp, int h, int w, const Taps &taps, int grid, hipStream_t st)
+{
+    hipLaunchKernelGGL((blur_pass_kernel<0, StoreAs<T>>), dim3(grid), dim3(256), 0, st, static_cast<const T *>(in),
+                       static_cast<T *>(tmp), h, w, 1, taps);
+    hipLaunchKernelGGL((blur_pass_kernel<1, StoreAs<T>>), dim3(grid), dim3(256), 0, st, static_cast<const T *>(tmp),
+                       static_cast<T *>(out), h, w, 1, taps);
+}
+}  // namespace
+
+PXSOM_EXPORT int pxsom_gaussian_blur_plane(const void *in_dev, void *out_dev, void *tmp_dev, int h, int w, int dtype,
+                                           const double *weights_host, int radius, void *stream)
+{
+    if (!in_dev || !out_dev || !tmp_dev || !weights_host || h < 1 || w < 1 || tmp_dev == in_dev || tmp_dev == out_dev)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_gaussian_blur_plane: bad arguments");
+    if (dtype != PXSOM_SEG_U8 && dtype != PXSOM_SEG_I16 && dtype != PXSOM_SEG_U16 && dtype != PXSOM_SEG_I32 &&
+        dtype != PXSOM_SEG_F32)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_gaussian_blur_plane: dtype %d is not u8 / i16 / u16 / i32 / f32", dtype);
+    if (radius < 0 || radius > kMaxRadius)
+        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_gaussian_blur_plane: radius %d outside [0, %d]", radius, kMaxRadius);
+    Taps taps;
+    taps.radius = radius;
+    for (int d = 0; d <= radius; d++) taps.w[d] = weights_host[radius + d];
+    for (int d = radius + 1; d <= kMaxRadius; d++) taps.w[d] = 0.0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int grid = (int)std::min<int64_t>(((int64_t)h * w + 255) / 256, (int64_t)pxsom::device_cu_count() * 16);
+    switch (dtype) {
+    case PXSOM_SEG_U8: launch_plane_blur<uint8_t>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
+    case PXSOM_SEG_I16: launch_plane_blur<int16_t>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
+    case PXSOM_SEG_U16: launch_plane_blur<uint16_t>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
+    case PXSOM_SEG_I32: launch_plane_blur<int32_t>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
+    default: launch_plane_blur<float>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
+    }
+    PXSOM_LAUNCH_CHECK("blur_pass_kernel (plane)");
+    return PXSOM_OK;
+}
+
+// ---- img[i] = 0 where seg[i] > 0 (exclude) or seg[i] == 0 (include): filter_with_nuclear_mask ----
+namespace {
+template <typename TI, typename TS>
+__global__ __launch_bounds__(256) void zero_by_seg_kernel(TI *__restrict__ img, const TS *__restrict__ seg, int64_t n,
+                                                          int exclude)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const TS s = seg[i];
+        if (exclude ? s > (TS)0 : s == (TS)0) img[i] = (TI)0;
+    }
+}
+
+template <typename TI>
+void launch_zero_by_seg(void *img, const void *seg, int seg_dtype, int64_t n, int exclude, int grid, hipStream_t st)
+{
+    TI *im = static_cast<TI *>(img);
+#define PXSOM_ZERO_BY(TS) \
+    hipLaunchKernelGGL((zero_by_seg_kernel<TI, TS>), dim3(grid), dim3(256), 0, st, im, static_cast<const TS *>(seg), n, exclude)
+    switch (seg_dtype) {
+    case PXSOM_SEG_U8: PXSOM_ZERO_BY(uint8_t); break;
+    case PXSOM_SEG_I16: PXSOM_ZERO_BY(int16_t); break;
+    case PXSOM_SEG_U16: PXSOM_ZERO_BY(uint16_t); break;
+    case PXSOM_SEG_I32: PXSOM_ZERO_BY(int32_t); break;
+    case PXSOM_SEG_U32: PXSOM_ZERO_BY(uint32_t); break;
+    default: PXSOM_ZERO_BY(int64_t); break;
+    }
+#undef PXSOM_ZERO_BY
+}
+}  // namespace
+
+PXSOM_EXPORT int pxsom_zero_by_seg(void *img_dev, int img_dtype, const void *seg_dev, int seg_dtype, int64_t n,
+                                   int exclude, void *stream)
+{
+    if (n < 0 || (n > 0 && (!img_dev || !seg_dev)) || (exclude != 0 && exclude != 1))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_zero_by_seg: bad arguments");
+    if (img_dtype != PXSOM_SEG_U8 && img_dtype != PXSOM_SEG_I16 && img_dtype != PXSOM_SEG_U16 && img_dtype != PXSOM_SEG_I32 &&
+        img_dtype != PXSOM_SEG_F32)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_zero_by_seg: image dtype %d is not u8 / i16 / u16 / i32 / f32", img_dtype);
+    if (seg_dtype < PXSOM_SEG_U8 || seg_dtype > PXSOM_SEG_I64)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_zero_by_seg: segmentation dtype %d is not u8 .. i64", seg_dtype);
+    if (n == 0) return PXSOM_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)pxsom::device_cu_count() * 16);
+    switch (img_dtype) {
+    case PXSOM_SEG_U8: launch_zero_by_seg<uint8_t>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
+    case PXSOM_SEG_I16: launch_zero_by_seg<int16_t>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
+    case PXSOM_SEG_U16: launch_zero_by_seg<uint16_t>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
+    case PXSOM_SEG_I32: launch_zero_by_seg<int32_t>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
+    default: launch_zero_by_seg<float>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
+    }
+    PXSOM_LAUNCH_CHECK("zero_by_seg_kernel");
     return PXSOM_OK;
 }
 

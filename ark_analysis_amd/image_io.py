@@ -101,6 +101,94 @@ def read_image(path, out=None) -> np.ndarray:
         return np.array(im)
 
 
+# TIFF SampleFormat (1 unsigned, 2 signed, 3 float) and BitsPerSample -> numpy kind
+_SAMPLE_KINDS = {1: "u", 2: "i", 3: "f"}
+
+
+def _tiff_directory(path):
+    """``(byte order, {tag: values})`` of the first image directory of a classic TIFF, plus whether more pages follow."""
+    import struct
+    with open(path, "rb") as f:
+        head = f.read(8)
+        if len(head) < 8 or head[:2] not in (b"II", b"MM"):
+            raise ValueError("%s is not a TIFF file" % path)
+        bo = "<" if head[:2] == b"II" else ">"
+        magic, first = struct.unpack(bo + "HI", head[2:8])
+        if magic != 42:
+            return bo, None, False          # BigTIFF: left to Pillow
+        f.seek(first)
+        (count,) = struct.unpack(bo + "H", f.read(2))
+        raw = f.read(12 * count + 4)
+        sizes = {1: ("B", 1), 2: ("s", 1), 3: ("H", 2), 4: ("I", 4), 16: ("Q", 8)}
+        tags = {}
+        for i in range(count):
+            tag, kind, n = struct.unpack(bo + "HHI", raw[12 * i:12 * i + 8])
+            if kind not in sizes:
+                continue
+            code, size = sizes[kind]
+            body = raw[12 * i + 8:12 * i + 12]
+            if n * size > 4:
+                (offset,) = struct.unpack(bo + "I", body)
+                f.seek(offset)
+                body = f.read(n * size)
+            tags[tag] = body[:n] if code == "s" else struct.unpack(bo + code * n, body[:n * size])
+        (next_ifd,) = struct.unpack(bo + "I", raw[12 * count:12 * count + 4])
+    return bo, tags, next_ifd != 0
+
+
+def _shape_description(tags):
+    """The array shape tifffile records in a page's ImageDescription (``{"shape": [...]}``), or None."""
+    import json
+    desc = tags.get(270)
+    if not desc:
+        return None
+    try:
+        meta = json.loads(bytes(desc).rstrip(b"\0").decode("ascii"))
+        return tuple(int(d) for d in meta["shape"])
+    except (ValueError, KeyError, TypeError, UnicodeDecodeError):
+        return None
+
+
+def read_tiff_shaped(path) -> np.ndarray:
+    """A single-page TIFF as a tifffile-based reader (``skimage.io.imread``) returns it: in the file's own dtype (int64
+    and the other 8-byte sample formats included) and in the shape its tifffile shape description records -- an array
+    saved as ``(1, H, W)`` keeps its leading axis, where :func:`read_image` gives ``(H, W)``.  Without such a
+    description the page's ``(H, W)``.  Uncompressed or deflate-compressed strips of one sample per pixel are read
+    here; anything else goes through :func:`read_image`.  Multi-page files are not supported."""
+    import zlib
+    bo, tags, more = _tiff_directory(path)
+    if more:
+        raise NotImplementedError("%s: multi-page TIFF files are not supported" % path)
+    arr = None
+    if tags is not None:
+        width, height = tags.get(256, (0,))[0], tags.get(257, (0,))[0]
+        bits = tags.get(258, (1,))[0]
+        kind = _SAMPLE_KINDS.get(tags.get(339, (1,))[0])
+        compression, predictor = tags.get(259, (1,))[0], tags.get(317, (1,))[0]
+        plain = (tags.get(277, (1,))[0] == 1 and 273 in tags and 279 in tags and kind is not None
+                 and bits in (8, 16, 32, 64) and compression in (1, 8, 32946) and predictor in (1, 2)
+                 and not (kind == "f" and (bits == 8 or predictor == 2)))
+        if plain:
+            dtype = np.dtype(bo + kind + str(bits // 8))
+            chunks = []
+            with open(path, "rb") as f:
+                for offset, nbytes in zip(tags[273], tags[279]):
+                    f.seek(offset)
+                    data = f.read(nbytes)
+                    chunks.append(zlib.decompress(data) if compression != 1 else data)
+            flat = np.frombuffer(b"".join(chunks), dtype=dtype)
+            if flat.size >= width * height:
+                arr = flat[:width * height].reshape(height, width).astype(dtype.newbyteorder("="))
+                if predictor == 2:          # horizontal differencing: running sums along each row, in the dtype
+                    arr = np.cumsum(arr, axis=1, dtype=arr.dtype)
+    if arr is None:
+        arr = read_image(path)
+    shape = _shape_description(tags or {})
+    if shape is not None and int(np.prod(shape)) == arr.size:
+        arr = arr.reshape(shape)
+    return arr
+
+
 def read_channel(tiff_dir, fov: str, channel: str, img_sub_folder: Optional[str] = None, out=None) -> np.ndarray:
     """One channel image ``[H, W]`` in the file's dtype."""
     return read_image(_channel_file(_fov_folder(tiff_dir, fov, img_sub_folder), channel), out=out)

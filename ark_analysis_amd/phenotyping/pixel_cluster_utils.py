@@ -2,8 +2,8 @@
 (/root/reference/src/ark/phenotyping/pixel_cluster_utils.py): row normalisation (:109-142), the
 per-cluster mean-expression table (:294-416), the restart helper (:419-478) and the TIFF-side percentiles
 that feed ``create_pixel_matrix`` (:16-106, :145-181; numpy's float32 arithmetic reproduced on the device).  Same names, arguments,
-error / warning texts and results; the TIFF-bound helpers of that module are out of scope (SURVEY.md
-section 8).  The per-cluster reduction is one accumulating device pass per FOV (pxsom_cluster_sums:
+error / warning texts and results.  The channel edits of notebook 2 (smooth_channels, filter_with_nuclear_mask,
+:183-291) blur / zero each plane on the device.  The per-cluster reduction is one accumulating device pass per FOV (pxsom_cluster_sums:
 binary64 sums, int64 counts) instead of a pandas groupby per FOV plus a groupby over the concatenation.
 """
 import os
@@ -74,6 +74,130 @@ def check_for_modified_channels(tiff_dir, test_fov, img_sub_folder, channels):
                               ' modified channels found: {}. Make sure you selected the correct '
                               'version of the channel for inclusion in '
                               'clustering'.format(channel, variant))
+
+
+# the image dtypes of som_device.PLANE_DTYPES and the label dtypes of som_device.SEG_DTYPES, as numpy dtypes
+_PLANE_DEVICE_DTYPES = tuple(np.dtype(d) for d in (np.uint8, np.int16, np.uint16, np.int32, np.float32))
+_SEG_DEVICE_DTYPES = tuple(np.dtype(d) for d in (np.uint8, np.int16, np.uint16, np.int32, np.uint32, np.int64))
+
+
+def _blur_device(planes, sigmas):
+    """scipy.ndimage.gaussian_filter(plane, sigma) of every host plane in its own dtype, on the device; host arrays
+    back.  The one device entry point of smooth_channels (the CPU tests swap it for scipy)."""
+    import torch
+    from .. import _capi, som_device
+    dev = _capi.require_gpu()
+    done = []
+    for plane, sigma in zip(planes, sigmas):
+        if plane.ndim != 2 or plane.dtype not in _PLANE_DEVICE_DTYPES:
+            raise NotImplementedError("smooth_channels on the device takes 2-D uint8, int16, uint16, int32 or float32 "
+                                      "images, got %s %s" % (plane.dtype, plane.shape))
+        t = torch.from_numpy(np.ascontiguousarray(plane)).to(dev)
+        done.append(som_device.gaussian_blur_plane(t, sigma, out=t))
+    return [t.cpu().numpy() for t in done]
+
+
+def _zero_device(img, seg, exclude):
+    """``img[seg > 0] = 0`` (``exclude``) or ``img[seg == 0] = 0`` for a host image and a segmentation of its shape, on
+    the device; host array back.  The one device entry point of filter_with_nuclear_mask (the CPU tests swap it)."""
+    import torch
+    from .. import _capi, som_device
+    dev = _capi.require_gpu()
+    if img.dtype not in _PLANE_DEVICE_DTYPES:
+        raise NotImplementedError("filter_with_nuclear_mask on the device takes uint8, int16, uint16, int32 or float32 "
+                                  "images, got %s" % img.dtype)
+    if seg.dtype not in _SEG_DEVICE_DTYPES:
+        # bool / int8 / uint64 / float labels: the comparison of the reference on the host, as a uint8 label image
+        seg = ((seg > 0) if exclude else (seg != 0)).astype(np.uint8)
+    t_img = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+    t_seg = torch.from_numpy(np.ascontiguousarray(seg)).to(dev)
+    return som_device.zero_by_segmentation(t_img, t_seg, exclude).cpu().numpy()
+
+
+def _edit_fovs(fovs, load, edit):
+    """``edit(fov, load(fov)) -> [(path, image), ...]`` over this rank's share of ``fovs``: the next FOV is loaded on a
+    helper thread while the current one is on the device, the images are written on a writer thread.  A failure
+    leaves the files of the FOVs before it written.  Under a process group every rank's files exist when this returns."""
+    import concurrent.futures
+    from .. import distributed
+    distributed.init_from_env()
+    mine = distributed.shard(fovs)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=1) as reader, \
+            concurrent.futures.ThreadPoolExecutor(max_workers=1) as writer:
+        written = []
+        ahead = reader.submit(load, mine[0]) if mine else None
+        for i, fov in enumerate(mine):
+            loaded = ahead.result()
+            ahead = reader.submit(load, mine[i + 1]) if i + 1 < len(mine) else None
+            written += [writer.submit(image_io.write_image, path, image) for path, image in edit(fov, loaded)]
+        for w in written:
+            w.result()
+    distributed.barrier()
+
+
+def smooth_channels(fovs, tiff_dir, img_sub_folder, channels, smooth_vals):
+    """Extra Gaussian blur of chosen channels (reference: pixel_cluster_utils.py:183-230): for every FOV and channel,
+    scipy.ndimage.gaussian_filter(image, sigma) in the image's own dtype, saved beside it as
+    ``<channel>_smoothed.tiff`` in that dtype.  ``smooth_vals``: one int for every channel, or a list with one sigma per
+    channel.  The blur runs on the device for sigma < 16.125 (radius <= 64); a larger sigma raises
+    NotImplementedError before any file is written.  Under a process group the FOVs are dealt out by rank."""
+    from .. import som_device
+    if channels is None or len(channels) == 0:
+        return
+    if img_sub_folder is None:
+        img_sub_folder = ''
+    if type(smooth_vals) is int:
+        smooth_vals = [smooth_vals for _ in range(len(channels))]
+    elif type(smooth_vals) is list:
+        if len(smooth_vals) != len(channels):
+            raise ValueError("A list was provided for variable smooth_vals, but it does not "
+                             "have the same length as the list of channels provided")
+    else:
+        raise ValueError("Variable smooth_vals must be either a single integer or a list")
+    for sigma in smooth_vals:
+        som_device.check_blur_sigma(sigma)
+
+    def load(fov):
+        return [image_io.read_channel(tiff_dir, fov, chan, img_sub_folder) for chan in channels]
+
+    def edit(fov, planes):
+        out = _blur_device(planes, smooth_vals)
+        return [(os.path.join(tiff_dir, fov, img_sub_folder, chan + '_smoothed.tiff'), img)
+                for chan, img in zip(channels, out)]
+
+    _edit_fovs(fovs, load, edit)
+
+
+def filter_with_nuclear_mask(fovs, tiff_dir, seg_dir, channel, nuc_seg_suffix="_nuclear.tiff", img_sub_folder=None,
+                             exclude=True):
+    """Zeroes ``channel`` inside the nuclei (``exclude``: where the segmentation is > 0; saved as
+    ``<channel>_nuc_exclude.tiff``) or outside them (where it is 0; ``<channel>_nuc_include.tiff``), in the image's
+    dtype (reference: pixel_cluster_utils.py:233-291).  The segmentation ``<seg_dir>/<fov><nuc_seg_suffix>`` is read as
+    skimage's imread returns it and indexed ``[0, ...]``, as the reference does: a ``(1, H, W)`` file (what
+    ``skimage.io.imsave`` makes of a ``(1, H, W)`` array) gives the ``(H, W)`` mask, zeroed on the device.  A plain 2-D
+    file gives its FIRST ROW, applied with numpy exactly as the reference applies it: it zeroes whole rows of the
+    image when H == W and raises IndexError otherwise.  Under a process group the FOVs are dealt out by rank."""
+    if seg_dir is None:
+        print('No seg_dir provided, you must provide one to run nuclear filtering')
+        return
+    validate_paths(seg_dir)
+    if img_sub_folder is None:
+        img_sub_folder = ''
+    suffix = "_nuc_exclude.tiff" if exclude else "_nuc_include.tiff"
+
+    def load(fov):
+        img = image_io.read_channel(tiff_dir, fov, channel, img_sub_folder)
+        return img, image_io.read_tiff_shaped(os.path.join(seg_dir, f"{fov}{nuc_seg_suffix}"))[0, ...]
+
+    def edit(fov, loaded):
+        img, seg = loaded
+        if seg.shape == img.shape:
+            img = _zero_device(img, seg, exclude)
+        else:
+            img[seg > 0 if exclude else seg == 0] = 0
+        return [(os.path.join(tiff_dir, fov, img_sub_folder, channel + suffix), img)]
+
+    _edit_fovs(fovs, load, edit)
 
 
 def normalize_rows(pixel_data, channels, include_seg_label=True):

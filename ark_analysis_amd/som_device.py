@@ -672,6 +672,64 @@ def segmentation_mask(seg: torch.Tensor, erode: Optional[str] = None, connectivi
     return out
 
 
+# pxsom_gaussian_blur_plane / pxsom_zero_by_seg: the plane dtypes (PXSOM_SEG_* codes, float32 = PXSOM_SEG_F32)
+PLANE_DTYPES = {torch.uint8: 0, torch.int16: 1, torch.uint16: 2, torch.int32: 3, torch.float32: 7}
+BLUR_MAX_RADIUS = 64                     # kMaxRadius of csrc/pxsom_pre.hip
+BLUR_SIGMA_LIMIT = 16.125                # int(4 sigma + 0.5) <= 64  <=>  sigma < 16.125
+
+
+def check_blur_sigma(sigma: float) -> None:
+    """NotImplementedError for a sigma whose radius the device blur does not take (sigma >= 16.125)."""
+    if float(sigma) > 1e-15 and int(4.0 * float(sigma) + 0.5) > BLUR_MAX_RADIUS:
+        raise NotImplementedError("gaussian blur on the device: sigma %r is beyond the radius limit "
+                                  "(sigma < %g, radius <= %d)" % (sigma, BLUR_SIGMA_LIMIT, BLUR_MAX_RADIUS))
+
+
+def gaussian_blur_plane(plane: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None,
+                        tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(plane, sigma) of a contiguous ``[H, W]`` HBM plane in its own dtype (uint8, int16,
+    uint16, int32 or float32): each pass stored in that dtype, as scipy stores it.  sigma <= 1e-15 skips both axes
+    (scipy's rule): the result is a copy.  ``out`` may be ``plane`` itself."""
+    if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in PLANE_DTYPES:
+        raise ValueError("plane must be a contiguous 2-D uint8 / int16 / uint16 / int32 / float32 HBM tensor")
+    h, w = plane.shape
+    if h == 0 or w == 0:
+        raise ValueError("plane must not be empty")
+    check_blur_sigma(sigma)
+    if out is None:
+        out = torch.empty_like(plane)
+    elif out.shape != plane.shape or out.dtype != plane.dtype or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous HBM tensor of the plane's shape and dtype")
+    if float(sigma) <= 1e-15:
+        if out.data_ptr() != plane.data_ptr():
+            out.copy_(plane)
+        return out
+    if tmp is None:
+        tmp = torch.empty_like(plane)
+    elif tmp.shape != plane.shape or tmp.dtype != plane.dtype or not tmp.is_cuda or not tmp.is_contiguous():
+        raise ValueError("tmp must be a contiguous HBM tensor of the plane's shape and dtype")
+    weights, radius = gaussian_kernel1d(float(sigma))
+    rc = _capi.lib().pxsom_gaussian_blur_plane(plane.data_ptr(), out.data_ptr(), tmp.data_ptr(), h, w,
+                                               PLANE_DTYPES[plane.dtype], weights.ctypes.data, radius, _capi.stream_ptr())
+    _capi.check(rc, "pxsom_gaussian_blur_plane")
+    return out
+
+
+def zero_by_segmentation(img: torch.Tensor, seg: torch.Tensor, exclude: bool = True) -> torch.Tensor:
+    """In place: ``img[seg > 0] = 0`` (``exclude``) or ``img[seg == 0] = 0`` for a contiguous HBM image (uint8, int16,
+    uint16, int32 or float32) and a contiguous segmentation of the same shape (uint8 .. int64)."""
+    if not img.is_cuda or not img.is_contiguous() or img.dtype not in PLANE_DTYPES:
+        raise ValueError("img must be a contiguous uint8 / int16 / uint16 / int32 / float32 HBM tensor")
+    if not seg.is_cuda or not seg.is_contiguous() or seg.dtype not in SEG_DTYPES:
+        raise ValueError("seg must be a contiguous uint8 / int16 / uint16 / int32 / uint32 / int64 HBM tensor")
+    if seg.shape != img.shape:
+        raise ValueError("img and seg must have the same shape, got %s and %s" % (tuple(img.shape), tuple(seg.shape)))
+    rc = _capi.lib().pxsom_zero_by_seg(img.data_ptr(), PLANE_DTYPES[img.dtype], seg.data_ptr(), SEG_DTYPES[seg.dtype],
+                                       img.numel(), 1 if exclude else 0, _capi.stream_ptr())
+    _capi.check(rc, "pxsom_zero_by_seg")
+    return img
+
+
 class AssignSumsWorkspace:
     """Scratch for pxsom_assign_sums, reusable across calls of the same (n_max, c, k)."""
 

@@ -481,6 +481,7 @@ int pxsom_train_online_metric(const void *x_dev, int64_t n, int c, int64_t ldx, 
 #define PXSOM_SEG_U32 4
 #define PXSOM_SEG_I64 5
 #define PXSOM_SEG_F64 6      /* output only */
+#define PXSOM_SEG_F32 7      /* pxsom_gaussian_blur_plane / pxsom_zero_by_seg images only */
 #define PXSOM_SEG_ERODE_NONE 0
 #define PXSOM_SEG_ERODE_THICK 1
 #define PXSOM_SEG_ERODE_INNER 2
@@ -490,6 +491,28 @@ int pxsom_segmask(const void *seg_dev, int seg_dtype, int h, int w, int64_t ld, 
                   int64_t background, const int32_t *keys_dev, const void *values_dev, int64_t n_keys, int32_t key_min,
                   int32_t key_max, double unassigned, void *out_dev, int out_dtype, int64_t ldo, void *workspace_dev,
                   size_t workspace_bytes, int flags, void *stream);
+
+/* ---- channel edits: smooth_channels and filter_with_nuclear_mask (K11) ----------------------------------------------
+ * The PXSOM_SEG_* codes name the dtypes of both entries.  Which entry takes which code:
+ *   pxsom_segmask              seg: U8 .. I64          out: I16, I32, F64 or seg's own
+ *   pxsom_gaussian_blur_plane  plane: U8, I16, U16, I32, F32
+ *   pxsom_zero_by_seg          img: U8, I16, U16, I32, F32    seg: U8 .. I64
+ *
+ * pxsom_gaussian_blur_plane: scipy.ndimage.gaussian_filter(plane, sigma) on ONE contiguous [h, w] plane in the plane's
+ * own dtype (reference: pixel_cluster_utils.smooth_channels).  Axis 0, then axis 1; each pass computes in binary64 in
+ * scipy's symmetric-kernel order without FMA contraction (as pxsom_gaussian_blur_hwc) and stores its result in the
+ * plane's dtype, as scipy stores each pass in the output array: float32 rounds to nearest, integers truncate toward zero
+ * (a C cast).  weights_host / radius as for pxsom_gaussian_blur_hwc; radius > 64 (sigma >= 16.125 at truncate 4) is
+ * PXSOM_ERR_UNSUPPORTED.  out_dev may equal in_dev; tmp_dev is a same-size plane of the same dtype, distinct from both.
+ * (Skipping an axis for sigma <= 1e-15 is the caller's: this entry always runs both passes.)
+ *
+ * pxsom_zero_by_seg: img[i] = 0 where seg[i] > 0 (exclude = 1) or seg[i] == 0 (exclude = 0), i < n; img and seg hold n
+ * elements each, contiguous (filter_with_nuclear_mask's img[seg > 0] = 0 / img[seg == 0] = 0).
+ * Bad pointers, sizes, dtype codes or flags: PXSOM_ERR_INVALID_ARG before any HIP call, for both entries. */
+int pxsom_gaussian_blur_plane(const void *in_dev, void *out_dev, void *tmp_dev, int h, int w, int dtype,
+                              const double *weights_host, int radius, void *stream);
+int pxsom_zero_by_seg(void *img_dev, int img_dtype, const void *seg_dev, int seg_dtype, int64_t n, int exclude,
+                      void *stream);
 
 #ifdef __cplusplus
 }
