@@ -14,7 +14,7 @@ _ROOT = os.path.dirname(_PKG)
 SO_PATH = os.path.join(_PKG, "libpxsom.so")
 SOURCES = ["pxsom_api.hip", "pxsom_assign.hip", "pxsom_assign_filter.hip", "pxsom_assign_filter_acc.hip", "pxsom_batch_step.hip", "pxsom_batch_step_wide.hip", "pxsom_train.hip",
            "pxsom_pre.hip", "pxsom_sums.hip", "pxsom_comm.hip", "pxsom_metric.hip",
-           "pxsom_segmask.hip"]
+           "pxsom_segmask.hip", "pxsom_cellquant.hip"]
 # per-file extra flags: the filter works on provably finite scores (see the file header)
 EXTRA_FLAGS = {"pxsom_assign_filter.hip": ["-ffinite-math-only"] + (
     ["-DSGB_VALU=" + os.environ["PXSOM_SGB_VALU"]] if "PXSOM_SGB_VALU" in os.environ else []) + (

@@ -105,6 +105,11 @@ SYMBOLS = {
                              _f64, _vp, _i32, _i64, _vp, _sz, _i32, _vp]),
     "pxsom_gaussian_blur_plane": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp]),
     "pxsom_zero_by_seg": (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _vp]),
+    "pxsom_cellquant_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i64, ctypes.c_int32, ctypes.c_int32, _i64,
+                                              ctypes.c_int32, ctypes.c_int32, _i32]),
+    "pxsom_cellquant": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i64, ctypes.c_int32,
+                               ctypes.c_int32, _vp, _i64, ctypes.c_int32, ctypes.c_int32, _i32, _f64, _i32, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
 }
 
 _lib = None

@@ -792,3 +792,115 @@ def assign_means(x: torch.Tensor, w: torch.Tensor, labels: torch.Tensor, sums: t
                                            workspace.buf.data_ptr(), workspace.bytes, flags, _capi.stream_ptr())
     _capi.check(rc, "pxsom_assign_means_ex")
     workspace.clean = n > 0 or not flags   # as assign_sums
+
+
+# pxsom_cellquant (K12): image dtypes (PXSOM_SEG_* codes) and modes
+CELLQUANT_IMAGE_DTYPES = {torch.uint8: 0, torch.int16: 1, torch.uint16: 2, torch.int32: 3, torch.float64: 6,
+                          torch.float32: 7}
+CELLQUANT_MODES = {"total_intensity": 0, "positive_pixel": 1, "center_weighting": 2}
+CELLQUANT_FORCE_SEARCH = 1
+CELLQUANT_NUC_CAPACITY = 128
+
+
+def label_keys(seg: torch.Tensor) -> torch.Tensor:
+    """The sorted unique nonzero labels of an HBM label image as the int32 key table of :func:`cell_quantify`.
+    Labels must be positive int32 values (NotImplementedError otherwise: negative labels and labels past int32 have no
+    cell-table row the reference's int32 label column could name)."""
+    wide = seg if seg.dtype in (torch.int32, torch.int64) else seg.to(
+        torch.int64 if seg.dtype == torch.uint32 else torch.int32)
+    keys = torch.unique(wide, sorted=True)
+    if keys.numel():
+        lo, hi = (int(v) for v in keys[[0, -1]].cpu())
+        if lo < 0 or hi > 2147483647:
+            raise NotImplementedError("cell table: labels must lie in 0 .. 2147483647, got %d .. %d" % (lo, hi))
+        if lo == 0:
+            keys = keys[1:]
+    return keys.to(torch.int32)
+
+
+def _label_image(seg: torch.Tensor, what: str):
+    if seg.dim() != 2 or not seg.is_cuda or seg.dtype not in SEG_DTYPES:
+        raise ValueError("%s must be a 2-D uint8 / int16 / uint16 / int32 / uint32 / int64 HBM tensor" % what)
+    h, w = seg.shape
+    if h == 0 or w == 0:
+        raise ValueError("%s must not be empty" % what)
+    if w > 1 and seg.stride(1) != 1:
+        raise ValueError("%s rows must be contiguous (stride(1) == 1)" % what)
+    return h, w, seg.stride(0) if h > 1 else w
+
+
+def _key_range(keys: torch.Tensor):
+    if keys.dtype != torch.int32 or keys.dim() != 1 or not keys.is_cuda or not keys.is_contiguous():
+        raise ValueError("keys must be a contiguous int32 HBM vector")
+    if keys.numel() == 0:
+        return 0, 0
+    lo, hi = (int(v) for v in keys[[0, -1]].cpu())
+    return lo, hi
+
+
+def cell_quantify(seg: torch.Tensor, img: torch.Tensor, keys: Optional[torch.Tensor] = None,
+                  mode: str = "total_intensity", threshold: float = 0.0, nuc: Optional[torch.Tensor] = None,
+                  nuc_keys: Optional[torch.Tensor] = None, nuc_capacity: int = 0, force_search: bool = False) -> dict:
+    """One pass of pxsom_cellquant: the per-cell table of a ``[H, W]`` label image (any row stride) over a contiguous
+    ``[H, W, C]`` (or ``[H, W]``) HBM image.  ``keys`` (default :func:`label_keys` of ``seg``) name the cells, sorted
+    ascending, unique and positive.  Returns a dict of HBM tensors: ``keys``, ``count`` [n] int64, ``sums`` [n, 2] int64
+    (row, column), ``bbox`` [n, 4] int32 (row min, row max, column min, column max), ``values`` [n, C] float64 (``mode``
+    total_intensity / positive_pixel with ``threshold``, compared in binary64 / center_weighting), and with a nuclear
+    label image ``nuc``: ``nuc`` [n] int32, the index in ``nuc_keys`` (default :func:`label_keys` of ``nuc``, also
+    returned as ``nuc_keys``) of the nucleus with the most pixels in the cell, the smaller on a tie, -1 for none.
+    ``nuc_capacity`` bounds the per-cell overlap table (0: 128); ``force_search`` takes the binary-search route for
+    both key tables."""
+    h, w, ld = _label_image(seg, "seg")
+    if img.dim() == 2:
+        img = img.unsqueeze(-1)
+    if img.dim() != 3 or tuple(img.shape[:2]) != (h, w) or not img.is_cuda or not img.is_contiguous() or \
+            img.dtype not in CELLQUANT_IMAGE_DTYPES:
+        raise ValueError("img must be a contiguous [H, W, C] uint8 / int16 / uint16 / int32 / float32 / float64 HBM "
+                         "tensor of the segmentation's height and width")
+    c = img.shape[2]
+    if c == 0:
+        raise ValueError("img must have at least one channel")
+    if mode not in CELLQUANT_MODES:
+        raise ValueError("mode must be one of %s" % sorted(CELLQUANT_MODES))
+    if keys is None:
+        keys = label_keys(seg)
+    kmin, kmax = _key_range(keys)
+    n = keys.numel()
+    if n and kmin <= 0:
+        raise ValueError("keys must be positive")
+    dev = seg.device
+    out = {"keys": keys,
+           "count": torch.empty(n, dtype=torch.int64, device=dev),
+           "sums": torch.empty((n, 2), dtype=torch.int64, device=dev),
+           "bbox": torch.empty((n, 4), dtype=torch.int32, device=dev),
+           "values": torch.empty((n, c), dtype=torch.float64, device=dev)}
+    n_nuc, nmin, nmax, ldn, nuc_code = -1, 0, 0, w, 0
+    if nuc is not None:
+        if tuple(nuc.shape) != (h, w):
+            raise ValueError("nuc must have the segmentation's shape")
+        _, _, ldn = _label_image(nuc, "nuc")
+        nuc_code = SEG_DTYPES[nuc.dtype]
+        if nuc_keys is None:
+            nuc_keys = label_keys(nuc)
+        nmin, nmax = _key_range(nuc_keys)
+        n_nuc = nuc_keys.numel()
+        if n_nuc and nmin <= 0:
+            raise ValueError("nuc_keys must be positive")
+        out["nuc_keys"] = nuc_keys
+        out["nuc"] = torch.empty(n, dtype=torch.int32, device=dev)
+    if not 0 <= int(nuc_capacity) <= CELLQUANT_NUC_CAPACITY:
+        raise ValueError("nuc_capacity must lie in 0 .. %d" % CELLQUANT_NUC_CAPACITY)
+    flags = CELLQUANT_FORCE_SEARCH if force_search else 0
+    img_code, mode_code = CELLQUANT_IMAGE_DTYPES[img.dtype], CELLQUANT_MODES[mode]
+    lib = _capi.lib()
+    wsb = lib.pxsom_cellquant_workspace_bytes(h, w, c, img_code, mode_code, n, kmin, kmax, n_nuc, nmin, nmax, flags)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    rc = lib.pxsom_cellquant(seg.data_ptr(), SEG_DTYPES[seg.dtype], ld, nuc.data_ptr() if nuc is not None else None,
+                             nuc_code, ldn, h, w, img.data_ptr(), img_code, c, keys.data_ptr() if n else None, n, kmin,
+                             kmax, nuc_keys.data_ptr() if nuc is not None and n_nuc > 0 else None, n_nuc, nmin, nmax,
+                             mode_code, float(threshold), int(nuc_capacity), out["count"].data_ptr(),
+                             out["sums"].data_ptr(), out["bbox"].data_ptr(), out["values"].data_ptr(),
+                             out["nuc"].data_ptr() if nuc is not None else None, ws.data_ptr(), wsb, flags,
+                             _capi.stream_ptr())
+    _capi.check(rc, "pxsom_cellquant")
+    return out

@@ -514,6 +514,44 @@ int pxsom_gaussian_blur_plane(const void *in_dev, void *out_dev, void *tmp_dev, 
 int pxsom_zero_by_seg(void *img_dev, int img_dtype, const void *seg_dev, int seg_dtype, int64_t n, int exclude,
                       void *stream);
 
+/* ---- cell table: per-cell counts, centroid sums and channel values of a segmented image (K12) -----------------------
+ * reference: ark/segmentation/marker_quantification.py compute_marker_counts under fast_extraction (regionprops label,
+ * coords, centroid) with ark/segmentation/signal_extraction.py and segmentation_utils.find_nuclear_label_id.
+ * seg_dev [h, w] (row stride ld >= w) of seg_dtype PXSOM_SEG_U8 .. PXSOM_SEG_I64; img_dev a contiguous interleaved
+ * [h, w, c] image of img_dtype PXSOM_SEG_U8, _I16, _U16, _I32, _F32 or _F64.  keys_dev [n_keys] int32, sorted ascending
+ * without duplicates and without 0, key_min = keys[0], key_max = keys[n_keys - 1] (not checked here: the Python wrapper
+ * does); cell i is the set of pixels whose label, cast to int32, equals keys[i] (label 0 is background).  Outputs per cell i:
+ *   count_dev[i] (int64)          pixels of the cell
+ *   sums_dev[2i], [2i + 1]        sum of row and of column indices (int64, exact; centroid = sum / count in binary64)
+ *   bbox_dev[4i .. 4i + 3]        row min, row max, column min, column max (int32; INT32_MAX, -1 for an absent key)
+ *   values_dev[i * c + j]         channel j as binary64, by mode:
+ *     PXSOM_CELLQUANT_TOTAL     np.sum(img[rows, cols], axis=0) in the image's dtype: integers exactly, float32 / float64
+ *                               in numpy's order -- for c >= 2 the pixels one after another in raster order, for c == 1
+ *                               numpy's pairwise sum over buffers of 8192 (bit-equal)
+ *     PXSOM_CELLQUANT_POSITIVE  count of img > threshold (compared in binary64: for a float32 image pass the threshold
+ *                               rounded to float32, as numpy compares)
+ *     PXSOM_CELLQUANT_CENTER    w . img[rows, cols] in binary64, w = 1 - d / (max d + 1), d the Chebyshev distance to the
+ *                               centroid; summed in raster order (the reference's BLAS order is not reproduced)
+ * nuc_dev (optional, [h, w], row stride ldn, nuc_dtype, keys nuc_keys_dev as for keys_dev): nuc_out_dev[i] = index in
+ * nuc_keys of the nucleus with the most pixels in cell i, the smaller index on a tie, -1 when none.  The overlap table
+ * holds nuc_capacity distinct nuclei per cell (1 .. 128, 0 = 128); a cell meeting more takes a slower exact route.
+ * Workspace: pxsom_cellquant_workspace_bytes with the same sizes, table ranges and flags (n_nuc_keys < 0: no nuclear image);
+ * key tables take a dense LUT by the K10 rule unless PXSOM_CELLQUANT_FORCE_SEARCH; both routes give identical results.
+ * Bad pointers, dtype codes, sizes, modes, flags or workspace: PXSOM_ERR_INVALID_ARG before any HIP call. */
+#define PXSOM_CELLQUANT_TOTAL 0
+#define PXSOM_CELLQUANT_POSITIVE 1
+#define PXSOM_CELLQUANT_CENTER 2
+#define PXSOM_CELLQUANT_FORCE_SEARCH 1
+size_t pxsom_cellquant_workspace_bytes(int h, int w, int c, int img_dtype, int mode, int64_t n_keys, int32_t key_min,
+                                       int32_t key_max, int64_t n_nuc_keys, int32_t nuc_key_min, int32_t nuc_key_max,
+                                       int flags);
+int pxsom_cellquant(const void *seg_dev, int seg_dtype, int64_t ld, const void *nuc_dev, int nuc_dtype, int64_t ldn,
+                    int h, int w, const void *img_dev, int img_dtype, int c, const int32_t *keys_dev, int64_t n_keys,
+                    int32_t key_min, int32_t key_max, const int32_t *nuc_keys_dev, int64_t n_nuc_keys,
+                    int32_t nuc_key_min, int32_t nuc_key_max, int mode, double threshold, int nuc_capacity,
+                    int64_t *count_dev, int64_t *sums_dev, int32_t *bbox_dev, double *values_dev, int32_t *nuc_out_dev,
+                    void *workspace_dev, size_t workspace_bytes, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
