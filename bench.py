@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- Pixie pixel-SOM train + assign throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
     (N > 1 without RANK in the environment: re-executes itself under torch.distributed.run, one rank per GPU;
      fails loudly when the box has fewer than N devices)
 
@@ -18,13 +18,18 @@ Workloads (`--config`; BASELINE.json configs):
   cfg5  FOVs 2048x2048x40 fp16, 20x20 SOM                (configs[4]; `--fovs-per-gpu`, default 4)
 Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else runs.  What it
+reports beside the headline comes from the timed steps themselves or from recorded files:
   roofline       dominant kernel = the BMU filter kernel over all rows; achieved = (C*s + 4) B/row (row read once +
                  int32 label written, DESIGN.md "K7") * rows / its HIP-event duration; traffic = HBM bytes per launch
                  from rocprofv3 PMC passes of this same script run inside the call (FETCH_SIZE x 2 + WRITE_SIZE, the
-                 gfx950 correction of MI355X_MICROARCH.md), or the recorded value if the profiler cannot run.
+                 gfx950 correction of MI355X_MICROARCH.md; --full), or the recorded value without them.
   roofline_step  the whole step against the HBM roofline: SURVEY 8(d)'s B = C*s*(1 + f*p) + 4 bytes per row.
-  mfma_util      matrix-pipe busy cycles / (SIMDs x kernel cycles) of the filter kernel, same PMC run.
+  mfma_util      matrix-pipe busy cycles / (SIMDs x kernel cycles) of the filter kernel, same PMC run (or recorded).
+--full adds every leg that takes runs of its own, after the timed steps:
+  phases_ms      train_batch / assign_and_mean_table: the same K steps once more with an event pair around each half;
+                 per_rank (N > 1): those per rank, replicas' codebooks compared, the exchange timed on its own.
+  operating_range, consensus (cfg5), and:
   cpu_baseline   the oracle (port of the reference algorithm: online FlowSOM training on the same
                  training subset + reference-shaped BMU search) on ONE host core; bounded sample.
   batch_train    the timed training mode's codebook against orc_som_batch at FULL size (rtol 1e-9).
@@ -85,6 +90,11 @@ def parse():
     ap.add_argument("--batch-steps", default="two-phase",
                     help="training schedule: 'two-phase' (default: 6 large steps while the radius is >= 1, 16 in "
                          "the BMU-only tail) or an integer = that many equal mini-batch steps per pass (64: rounds 1-2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg beside the headline: the phase run (phases_ms halves, per-rank "
+                         "phases and exchange timings), rocprofv3 counter passes, operating range, consensus (cfg5), CPU baseline, "
+                         "parity against the oracle, exact-online training (cfg1: the batch-mode leg and the CPU baseline); "
+                         "the --no-* options below leave out single legs of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-online", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (traffic / mfma_util)")
@@ -263,7 +273,10 @@ def run_cfg1(args):
     import contextlib
     import io
     legs = {}
-    for mode, kw in (("online", {}), ("batch", {"train_mode": "batch"})):     # reference order (exact) / the throughput rule
+    modes = [("online", {})]                                   # reference order (exact): the headline
+    if args.full or args.dump_outputs:                         # the throughput rule beside it (its arrays are part of the dump)
+        modes.append(("batch", {"train_mode": "batch"}))
+    for mode, kw in modes:
         times = []
         for i in range(args.warmup + args.steps):
             root = make_dirs()
@@ -283,15 +296,17 @@ def run_cfg1(args):
             "config": {"workload": "1 synthetic FOV 512x512x8ch, 10x10 SOM via train_pixel_som -> cluster_pixels -> generate_som_avg_files "
                                    "on binary64 feather tables (BASELINE.json configs[0]: the plumbing config)", "name": "cfg1",
                        "rows": n, "channels": c, "som_nodes": 100, "train_rows": int(len(sub)), "num_passes": 1}}
-    t_on, t_ba = legs["online"][0], legs["batch"][0]
+    t_on = legs["online"][0]
     line["value"] = round(n / float(np.sum(t_on)) / 1e6, 3)
     line["ms_per_step"] = round(float(np.sum(t_on)) * 1e3, 2)
     line["phases_ms"] = {"train_mode_online (reference order, exact)": {"train_pixel_som": round(t_on[0] * 1e3, 2), "cluster_pixels": round(t_on[1] * 1e3, 2),
-                                                                         "generate_som_avg_files": round(t_on[2] * 1e3, 2)},
-                         "train_mode_batch": {"train_pixel_som": round(t_ba[0] * 1e3, 2), "cluster_pixels": round(t_ba[1] * 1e3, 2),
-                                              "generate_som_avg_files": round(t_ba[2] * 1e3, 2), "Mpx_per_s": round(n / float(np.sum(t_ba)) / 1e6, 3)}}
+                                                                         "generate_som_avg_files": round(t_on[2] * 1e3, 2)}}
+    if "batch" in legs:
+        t_ba = legs["batch"][0]
+        line["phases_ms"]["train_mode_batch"] = {"train_pixel_som": round(t_ba[0] * 1e3, 2), "cluster_pixels": round(t_ba[1] * 1e3, 2),
+                                                 "generate_som_avg_files": round(t_ba[2] * 1e3, 2), "Mpx_per_s": round(n / float(np.sum(t_ba)) / 1e6, 3)}
     line["roofline"] = None     # host-side plumbing (feather I/O, DataFrames): no kernel of this run is priced against a roofline
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the same three calls with the oracle behind ark_analysis_amd.flowsom (test infrastructure, used here as the CPU baseline only)
         from tests import oracle_backend
         from ark_analysis_amd import flowsom
@@ -423,10 +438,6 @@ def main():
         step()
     fence()
     timer = _capi.KernelTimer(min_rows=n_all)
-    ev_train = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                for _ in range(args.steps)]
-    ev_k8 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-             for _ in range(args.steps)]
     # the timed region: exactly K steps between two fences, with the HIP events of the roofline's kernel timer (inside the library,
     # on the launch's stream) and nothing else
     with timer:
@@ -436,39 +447,50 @@ def main():
         fence()
         t1 = time.perf_counter()
         kern_ms, kern_launches = timer.collect()
-    if args.dump_outputs and rank == 0 and not args.pmc_inner:     # before the phase run below overwrites them
+    if args.dump_outputs and rank == 0 and not args.pmc_inner:     # before the phase run of --full overwrites them
         dump_outputs(args.dump_outputs, codebook=w, labels=labels, cluster_counts=k8_counts, cluster_means=means)
-    # the phases of a step: the same K steps once more, with an event pair around each half (four event records per step cost the
-    # stream 10 - 15 us: they are not part of the step and stay out of the timed region)
-    for i in range(args.steps):
-        ev_train[i][0].record()
-        trainer.train(x_train, w0, num_passes=1, out=w)
-        ev_train[i][1].record()
-        ev_k8[i][0].record()
-        assign_and_mean_table()
-        ev_k8[i][1].record()
-    fence()
+    train_ms = k8_ms = None
+    if args.full:
+        # the phases of a step: the same K steps once more, with an event pair around each half (four event records per step cost
+        # the stream 10 - 15 us: they are not part of the step and stay out of the timed region)
+        ev_train = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    for _ in range(args.steps)]
+        ev_k8 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                 for _ in range(args.steps)]
+        for i in range(args.steps):
+            ev_train[i][0].record()
+            trainer.train(x_train, w0, num_passes=1, out=w)
+            ev_train[i][1].record()
+            ev_k8[i][0].record()
+            assign_and_mean_table()
+            ev_k8[i][1].record()
+        fence()
+        train_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_train]))
+        k8_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_k8]))
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if use_dist:
         all_reduce_(elapsed, op=dist.ReduceOp.MAX)
     elapsed_s = float(elapsed.item())
-    train_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_train]))
-    k8_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_k8]))
     # (the one-pass kernel settles its listed rows inside the launch: no list to count afterwards)
     comm_ranks = 0
+    exchange_route = exchange_fused = None
     exact_rows = som_device.last_exact_rows(ws_all) if (not args.one_pass) or cfg["c"] > 32 or K != 100 else None
+    if use_dist:
+        from ark_analysis_amd.distributed import native_exchange
+        native = native_exchange(None)                                     # (made once per group: cached by now)
+        comm_ranks = world if native is not None else 0
+        exchange_route = type(native).__name__ if native is not None else "torch.distributed"
+        exchange_fused = bool(getattr(native, "fused", False))
 
     # every rank's own phase times (N > 1: the first multi-GPU line must be readable rank by rank)
     per_rank = None
-    if use_dist:
+    if use_dist and args.full:
         mine = torch.tensor([train_ms, k8_ms], dtype=torch.float64, device="cpu" if dry else dev)
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
         per_rank = {"train_batch": [round(float(g[0]), 4) for g in gathered],
                     "assign_and_mean_table": [round(float(g[1]), 4) for g in gathered]}
         from ark_analysis_amd import distributed as _dm
-        from ark_analysis_amd.distributed import native_exchange
-        native = native_exchange(None)                                     # (made once per group: cached by now)
         # replicas: every rank must hold the same codebook bit for bit after the timed passes
         wmine = w.detach().cpu() if dry else w.detach().clone()      # (gloo gathers host tensors, RCCL device tensors)
         copies = [torch.zeros_like(wmine) for _ in range(world)]
@@ -476,7 +498,6 @@ def main():
         per_rank["codebooks_equal"] = bool(all(torch.equal(cp, copies[0]) for cp in copies)) and bool(torch.isfinite(wmine).all().item())
         per_rank["kernel_route_agreement"] = getattr(trainer.kernels, "route_agreement", None)
         per_rank["exchange_decision"] = _dm.exchange_report.get(None)
-        comm_ranks = world if native is not None else 0
         assert dist.get_world_size() == args.gpus, "process group size and --gpus disagree"
         # the rule's only exchange, timed on its own after the timed region: one [K*C + K] binary64 all-reduce per step, back
         # to back on the route the pass uses -- what the training pass of an N-rank job pays on top of its kernels
@@ -493,8 +514,8 @@ def main():
         all_reduce_(exch, op=dist.ReduceOp.MAX)
         per_rank["exchange_us_per_step"] = round(float(exch.item()), 2)
         per_rank["exchange_ms_per_pass"] = round(float(exch.item()) * sched.steps * 1e-3, 4)
-        per_rank["exchange_route"] = type(native).__name__ if native is not None else "torch.distributed"
-        per_rank["exchange_fused"] = bool(getattr(native, "fused", False))
+        per_rank["exchange_route"] = exchange_route
+        per_rank["exchange_fused"] = exchange_fused
         # the other in-library route beside it: the one-shot peer-to-peer exchange over HIP IPC blocks (opt-in, PXSOM_EXCHANGE=p2p;
         # validated with two ranks on one device only -- no multi-GPU hardware number exists until a SCALE record holds one)
         p2p_us = (_dm.exchange_report.get(None) or {}).get("p2p_us_per_exchange")    # ("auto": both routes were timed when the communicator was made)
@@ -571,17 +592,17 @@ def main():
                    "rccl_ranks": (0 if dry else world) if use_dist else 0,
                    **({"dry_run": "all ranks on one GPU over gloo: exercises the N > 1 code, timings are meaningless"} if dry else {}),
                    "exchange": ((("in-library peer-to-peer exchange INSIDE the step launches (HIP IPC blocks; last workgroup writes, next step's prologue adds)"
-                                  if per_rank.get("exchange_fused") and cfg["kind"] != "cell" else
+                                  if exchange_fused and cfg["kind"] != "cell" else
                                   "in-library peer-to-peer all-reduce (HIP IPC blocks, one launch per rank) behind every step")
-                                 if per_rank and per_rank.get("exchange_route") == "P2PComm" else
+                                 if exchange_route == "P2PComm" else
                                  "in-library RCCL all-reduce behind every step") if comm_ranks else "torch.distributed all-reduce per step")
                    if use_dist else "none (one rank)"},
-        "phases_ms": {"train_batch": round(train_ms, 4),
-                      "assign_and_mean_table": round(k8_ms, 4),
+        "phases_ms": {**({"train_batch": round(train_ms, 4), "assign_and_mean_table": round(k8_ms, 4)} if args.full else {}),
                       "assign_filter_kernel": round(kern_avg_ms, 4),
                       "assign_exact_rows": exact_rows,
                       "passes_over_x": 2 if (not args.one_pass) else 1,
-                      "measured": "event pairs around the halves of the same K steps, run once more after the timed region",
+                      **({"measured": "event pairs around the halves of the same K steps, run once more after the timed region"}
+                         if args.full else {}),
                       **({"per_rank": per_rank} if per_rank else {})},
         "roofline": ({"kernel": "bmu_filter_kernel", "bound": "mfma", "achieved": round(achieved_tf, 1),
                       "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved_tf / MFMA_F16_PEAK_TFLOPS, 4),
@@ -603,9 +624,10 @@ def main():
                                   "(profiles/r04/assign_sums_size_probe.txt)" % (n_train * C * esize / 1e6)},
     }
 
-    # ---- HBM traffic and matrix-pipe utilisation of the filter kernel: PMC passes of a short run of this script
+    # ---- HBM traffic and matrix-pipe utilisation of the filter kernel: PMC passes of a short run of this script (--full), else
+    # the recorded values
     pmc = {}
-    if world == 1 and not args.no_pmc:
+    if args.full and world == 1 and not args.no_pmc:
         inner = ["--config", args.config, "--steps", "2", "--warmup", "1", "--batch-steps", str(args.batch_steps),
                  "--no-cpu-baseline", "--no-online", "--no-pmc", "--pmc-inner"] + ([] if args.one_pass else ["--two-pass"])
         if args.fovs_per_gpu:
@@ -638,7 +660,7 @@ def main():
                             "value": recorded[("onepass" if args.one_pass else "bmu_filter") + "_kernel_mfma_util"],
                             "source": "profiles/pmc_traffic.json (recorded; no in-run PMC pass)"}
 
-    if world == 1 and args.config == "cfg2" and not args.no_operating_range:
+    if args.full and world == 1 and args.config == "cfg2" and not args.no_operating_range:
         # Operating range of "bit-exact at HBM speed" (tests/tools/robustness_sweep.py holds the full sweep): the synthetic
         # workload lists 0.02 % of its rows for the exact path; codebooks made of data rows (distance-0 matches) and
         # codebooks with node pairs 1e-2 apart list far more.  Same rows, labels only (pxsom_assign), HIP-event timed.
@@ -686,7 +708,7 @@ def main():
         x_all = x_keep
         del x_keep
 
-    if args.config == "cfg5":
+    if args.full and args.config == "cfg5":
         # "+ consensus meta-cluster" (BASELINE.json configs[4]): Ward on the K x C mean table on the host (the
         # reference's PixieConsensusCluster step), then the K-entry lookup over the labels in HBM.  Outside the timed
         # step: reported beside it.
@@ -718,7 +740,7 @@ def main():
                             "meta_clusters_found": int(torch.unique(meta).numel()),
                             "note": "K x C table on the host (as the reference), K-entry lookup in HBM; not part of the timed step"}
 
-    if world == 1 and args.config != "cfg2" and not args.no_cpu_baseline:
+    if args.full and world == 1 and args.config != "cfg2" and not args.no_cpu_baseline:
         # The other configurations: the same oracle (online FlowSOM training + reference-shaped BMU search + per-cluster
         # sums, one host core) on a BOUNDED sample -- about 10 s of training steps and 10 s of row labelling -- scaled
         # linearly to the configuration's rows; the GPU labels of the sampled rows are compared on the way.
@@ -749,7 +771,7 @@ def main():
                       f"{n_all} rows, each scaled linearly; fp64, 1 thread",
             "gpu_labels_equal_on_sample": bool(np.array_equal(lab_gpu.cpu().numpy(), lab_cpu))}
 
-    if world == 1 and args.config == "cfg2":
+    if args.full and world == 1 and args.config == "cfg2":
         oracle_w = None
         order = None
         rr = default_radius_range(XD, YD)

@@ -193,6 +193,21 @@ def test_bench_picks_the_launch_over_all_rows_from_counter_rows():
     assert bench.select_launch_counters([], ["FETCH_SIZE"]) == {}
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    """A plain bench.py run is the headline only; the legs beside it run with --full."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("pxsom_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-pmc"])
+    a = bench.parse()
+    assert a.full is True and a.no_pmc is True
+
+
 def test_binary16_fixed_point_conversion_is_exact_for_every_finite_half():
     """The mean-table kernel turns a binary16 value into 2^-24 fixed point as bits(v + 1.5 * 2^28) - bits(1.5 * 2^28)
     (csrc/pxsom_train.hip, cluster_sums_kernel): checked here for all 63 488 finite bit patterns, signed zeros and

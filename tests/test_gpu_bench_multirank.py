@@ -40,7 +40,8 @@ def test_two_rank_bench_line(gpu, tmp_path, exchange, config):
         env.update(PXSOM_NATIVE_EXCHANGE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--config", config, "--fovs-per-gpu", "1", "--no-pmc", "--no-cpu-baseline", "--no-online", "--no-operating-range"]
+           "--config", config, "--fovs-per-gpu", "1", "--full", "--no-pmc", "--no-cpu-baseline", "--no-online",
+           "--no-operating-range"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, res.stdout[-2000:] + res.stderr[-4000:]
@@ -78,7 +79,8 @@ def test_four_rank_bench_line(gpu, tmp_path, config, exchange):
         env.update(PXSOM_EXCHANGE=exchange)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--config", config, "--fovs-per-gpu", "1", "--no-pmc", "--no-cpu-baseline", "--no-online", "--no-operating-range"]
+           "--config", config, "--fovs-per-gpu", "1", "--full", "--no-pmc", "--no-cpu-baseline", "--no-online",
+           "--no-operating-range"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=str(tmp_path))
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, res.stdout[-2000:] + res.stderr[-4000:]
