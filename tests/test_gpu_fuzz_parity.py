@@ -466,3 +466,235 @@ def test_fuzz_front_ends(oracle):
             want = oracle.som_online(host, host[init_idx], xdim, ydim, rlen, (0.05, 0.01),
                                      flowsom.default_radius_range(xdim, ydim), order)
             assert np.array_equal(got, want), tag + " som(seed=%d, rlen=%d)" % (seed, rlen)
+
+
+# ---- FlowSOM's other distances (distf 1, 3, 4): pxsom_assign_metric and pxsom_train_online_metric --------------------
+# The generators below are device-free (host arrays and plain parameters) so that test_fuzz_generators.py can check them
+# on a machine without a GPU.  Each draws from a RandomState of its own: _case / _rows / _codebook keep their streams.
+METRIC_REG_CHANNELS = 32            # kRegChannels of csrc/pxsom_metric.hip: wider rows are staged in LDS per 16 channels
+METRIC_ASSIGN_ROUTES = ("register", "staged")
+NP_DT = {"f32": np.float32, "f64": np.float64, "f16": np.float16}
+LABEL_SENTINEL = -0x5A5A5A5B        # guard-band fills: any store outside the caller's slice changes them
+DIST_SENTINEL = -1.2345678912345e300
+
+
+def metric_assign_route(c):
+    return "register" if c <= METRIC_REG_CHANNELS else "staged"
+
+
+def _storage(rs, host, dtype):
+    """(values as stored in `dtype`, their float64 twin, leading column offset, pad after the row)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        stored = np.ascontiguousarray(host, dtype=NP_DT[dtype])
+    return stored, stored.astype(np.float64), int(rs.choice([0, 0, 1, 2, 3, 5])), int(rs.choice([0, 0, 1, 3, 8]))
+
+
+def metric_assign_cases(seed, count):
+    """Cases of test_fuzz_metric_assign.  Case i takes route class i % 2 (register / staged, from c against 32) and metric
+    (i // 2) % 3, then draws the rest: c on the channel-chunk and node-tile edges, k up to 1024, storage type, row
+    offset and pad, value kind; about a third of the cases repeat the (c, k) of the last case of their class with fewer
+    rows, so that the workspace of that case is used again."""
+    rs = np.random.RandomState(seed)
+    last = {}
+    for i in range(count):
+        route = METRIC_ASSIGN_ROUTES[i % len(METRIC_ASSIGN_ROUTES)]
+        metric = (1, 3, 4)[(i // 2) % 3]
+        prev = last.get((route, metric))
+        if prev is not None and (rs.rand() < 0.35 or i % 12 == 7):
+            c, k, n_max = prev
+            n = int(rs.randint(1, n_max + 1))
+        else:
+            if route == "register":
+                c = int(rs.choice([1, 15, 16, 17, 31, 32])) if rs.rand() < 0.75 else int(rs.randint(1, 33))
+            else:
+                c = int(rs.choice([33, 47, 48, 49, 64, 127, 128, 129])) if rs.rand() < 0.8 else int(rs.randint(33, 1025))
+            u = rs.rand()
+            if u < 0.2:
+                k = 1024
+            elif u < 0.45:
+                k = 16 * int(rs.randint(0, 64)) + 1
+            elif u < 0.7:
+                k = 16 * int(rs.randint(0, 64)) + 15
+            else:
+                k = int(rs.randint(1, 1025))
+            n_max = int(max(1, min(20000, 3e7 / (k * c))))
+            n = int(rs.choice([1, 2, 63, 64, 65, 255, 256, 257])) if rs.rand() < 0.3 else int(rs.randint(1, n_max + 1))
+            n = min(n, n_max)
+            n_max = n
+        last[(route, metric)] = (c, k, n_max)
+        dtype = str(rs.choice(["f32", "f32", "f64", "f16"]))
+        kind = str(rs.choice(["mixture", "blob", "quantised", "sparse", "range", "wild"]))
+        stored, host, off, pad = _storage(rs, _rows(rs, n, c, kind), dtype)
+        w = _codebook(rs, host, k, kind)
+        if k > 1 and rs.rand() < 0.7:       # duplicated nodes with rows sitting on them: ties the first node must win
+            for _ in range(int(rs.randint(1, 9))):
+                a, b = np.sort(rs.choice(k, 2, replace=False))
+                w[b] = w[a]
+                r = int(rs.randint(0, n))
+                with np.errstate(over="ignore", invalid="ignore"):
+                    stored[r] = w[a].astype(stored.dtype)
+                host[r] = stored[r].astype(np.float64)
+        assert metric_assign_route(c) == route
+        yield dict(i=i, route=route, metric=metric, n=n, c=c, k=k, dtype=dtype, kind=kind, x=stored, host=host, w=w,
+                   off=off, pad=pad, guard=int(rs.randint(1, 40)), reuse=(c, k) == (prev or (0, 0))[:2])
+
+
+def _guarded(n, guard, dtype, fill, device):
+    buf = torch.full((guard + n + guard,), fill, dtype=dtype, device=device)
+    return buf, buf[guard:guard + n]
+
+
+def _outside_unchanged(buf, guard, n, fill):
+    """Every element of the guard bands still holds `fill`, bit for bit."""
+    b = buf.cpu().numpy()
+    bands = np.concatenate([b[:guard], b[guard + n:]])
+    want = np.full(bands.shape, fill, dtype=b.dtype)
+    return np.array_equal(bands.view(np.uint8), want.view(np.uint8))
+
+
+def test_fuzz_metric_assign():
+    """pxsom_assign_metric (Manhattan, Chebyshev, cosine) on random shapes around the register / staged boundary, the
+    16-channel chunks and the 16-node tiles, strided row views at column offsets, every storage type and value kind:
+    labels equal to tests/metric_reference.py, distances bit for bit, nothing stored outside the caller's slices, and a
+    workspace used again where its shape fits."""
+    from ark_analysis_amd import som_device
+    from tests import metric_reference as mr
+    dev = torch.device("cuda")
+    ws = {}
+    reused = 0
+    for case in metric_assign_cases(SEED + 20, CASES):
+        n, c, k, off, pad = case["n"], case["c"], case["k"], case["off"], case["pad"]
+        tag = "case %d: metric=%d route=%s n=%d c=%d k=%d %s %s off=%d pad=%d (PXSOM_FUZZ_SEED=%d)" % (
+            case["i"], case["metric"], case["route"], n, c, k, case["dtype"], case["kind"], off, pad, SEED)
+        buf = torch.zeros((n, off + c + pad), dtype=TORCH_DT[case["dtype"]])
+        buf[:, off:off + c] = torch.from_numpy(case["x"])
+        x = buf.to(dev)[:, off:off + c]
+        assert np.array_equal(x.cpu().to(torch.float64).numpy(), case["host"], equal_nan=True), tag + ": upload"
+        g = case["guard"]
+        lbuf, labels = _guarded(n, g, torch.int32, LABEL_SENTINEL, dev)
+        dbuf, dists = _guarded(n, g, torch.float64, DIST_SENTINEL, dev)
+        prev = ws.get((case["route"], case["metric"]))
+        fits = prev is not None and prev.fits(n, c, k, case["metric"])
+        reused += fits
+        som_device.assign(x, torch.from_numpy(case["w"]).to(dev), labels=labels, dists=dists, want_dists=True,
+                          workspace=prev if fits else None, metric=case["metric"])
+        ws[(case["route"], case["metric"])] = som_device.assign.last_workspace
+        assert som_device.assign.last_workspace is prev or not fits, tag + ": workspace not reused"
+        want_l, want_d = mr.map_data_to_nodes(case["w"], case["host"], case["metric"])
+        got_l, got_d = labels.cpu().numpy(), dists.cpu().numpy()
+        assert np.array_equal(got_l, want_l), tag + ": %d labels differ, first at row %s" % (
+            int((got_l != want_l).sum()), np.flatnonzero(got_l != want_l)[:3])
+        assert np.array_equal(got_d.view(np.int64), want_d.view(np.int64)), tag + ": distances differ at rows %s" % (
+            np.flatnonzero(got_d.view(np.int64) != want_d.view(np.int64))[:3])
+        assert _outside_unchanged(lbuf, g, n, LABEL_SENTINEL), tag + ": labels stored outside [0, n)"
+        assert _outside_unchanged(dbuf, g, n, DIST_SENTINEL), tag + ": distances stored outside [0, n)"
+    assert reused or CASES < 8, "no case used a workspace again"
+
+
+def online_metric_route(k, c):
+    """The launch of pxsom_train_online_metric for k nodes x c channels, by the rule of train_online_metric_typed and
+    launch_online (csrc/pxsom_train.hip): "register" (CMAX > 0: rows in registers, codebook in registers), "lds" (CMAX 0,
+    codebook in LDS beside the row ring), "in_place" (CMAX 0, the codebook does not fit: trained where it lies), or
+    "unsupported" (more than 1024 nodes or channels: PXSOM_ERR_UNSUPPORTED)."""
+    if k > 1024 or c > 1024:
+        return "unsupported"
+    if (k <= 256 and c <= 64) or (k <= 512 and c <= 40):
+        return "register"
+    bd = (k + 63) // 64 * 64
+    nwv = bd // 64
+
+    def plan(in_lds):
+        fixed = (c * k * 8 if in_lds else 0) + 2 * nwv * 8 + 2 * nwv * 4 + nwv * 8 + 2 * 64 * 8 + 64
+        chunk = 64
+        while chunk > 8 and fixed + 2 * chunk * c * 8 > 150 * 1024:
+            chunk >>= 1
+        while (chunk * c + bd - 1) // bd > 16:
+            chunk >>= 1
+        return chunk, fixed + 2 * chunk * c * 8
+
+    chunk, lds = plan(True)
+    if chunk < 1 or lds > 160 * 1024:
+        chunk, lds = plan(False)
+        assert chunk >= 1 and lds <= 160 * 1024
+        return "in_place"
+    return "lds"
+
+
+ONLINE_METRIC_ROUTES = ("register", "lds", "in_place", "unsupported")
+
+
+def metric_online_cases(seed, count):
+    """Cases of test_fuzz_metric_online: case i takes route class i % 4 of online_metric_route, metric (i // 4) % 3,
+    then a random grid and width inside that class, rlen 1 or 2, int_abs, storage type and value kind."""
+    rs = np.random.RandomState(seed)
+    for i in range(count):
+        route = ONLINE_METRIC_ROUTES[i % len(ONLINE_METRIC_ROUTES)]
+        metric = (1, 3, 4)[(i // 4) % 3]
+        for _ in range(1000):
+            if route == "unsupported":
+                xdim, ydim, c = int(rs.randint(33, 40)), int(rs.randint(32, 40)), int(rs.randint(1, 20))
+                if rs.rand() < 0.4:
+                    xdim, ydim, c = int(rs.randint(1, 10)), int(rs.randint(1, 10)), 1025
+            elif route == "register":
+                xdim, ydim = int(rs.randint(1, 23)), int(rs.randint(1, 23))
+                c = int(rs.choice([1, 7, 8, 9, 23, 24, 25, 39, 40, 41, 63, 64])) if rs.rand() < 0.7 else int(rs.randint(1, 65))
+            elif route == "lds":
+                xdim, ydim = int(rs.randint(1, 33)), int(rs.randint(1, 33))
+                c = int(rs.choice([41, 65, 128, 129, 200, 257, 512, 1024])) if rs.rand() < 0.6 else int(rs.randint(41, 1025))
+            else:
+                xdim, ydim = int(rs.randint(16, 33)), int(rs.randint(16, 33))
+                c = int(rs.choice([20, 24, 33, 40, 64, 100, 128, 129])) if rs.rand() < 0.6 else int(rs.randint(16, 200))
+            if online_metric_route(xdim * ydim, c) == route:
+                break
+        else:
+            raise AssertionError("no shape drawn for route %s" % route)
+        k = xdim * ydim
+        rlen = int(rs.choice([1, 2]))
+        int_abs = bool(rs.rand() < 0.5)
+        n = int(rs.randint(1, max(2, int(min(600, 1.5e5 / (c * rlen))))))
+        if route == "unsupported":
+            n = int(rs.randint(1, 50))
+        dtype = str(rs.choice(["f32", "f32", "f64", "f16"]))
+        kind = str(rs.choice(["mixture", "blob", "quantised", "sparse", "range"]))
+        rows = _rows(rs, n, c, kind) * (3.0 if int_abs else 1.0)
+        stored, host, off, pad = _storage(rs, rows, dtype)
+        w0 = host[rs.choice(n, k, replace=n < k)].copy() if route != "unsupported" else np.zeros((k, c))
+        if k > 3 and rs.rand() < 0.3:
+            w0[rs.randint(0, k)] = w0[rs.randint(0, k)]                   # a duplicated node
+        order = rs.randint(0, n, size=n * rlen).astype(np.int64)
+        yield dict(i=i, route=route, metric=metric, xdim=xdim, ydim=ydim, n=n, c=c, rlen=rlen, int_abs=int_abs,
+                   dtype=dtype, kind=kind, x=stored, host=host, w0=w0, order=order, off=off, pad=pad)
+
+
+def test_fuzz_metric_online():
+    """pxsom_train_online_metric on random grids (k <= 1024) and widths over each of its launches (rows in registers,
+    codebook in LDS, codebook trained where it lies), rlen 1 / 2, both readings of the early-stop accumulator, every
+    storage type: the codebook bit-equal to tests/metric_reference.py som_online.  Shapes past 1024 nodes or channels
+    must raise."""
+    from ark_analysis_amd import _capi, som_device
+    from ark_analysis_amd.flowsom import default_radius_range
+    from tests import metric_reference as mr
+    dev = torch.device("cuda")
+    for case in metric_online_cases(SEED + 21, CASES):
+        xdim, ydim, n, c, off, pad = case["xdim"], case["ydim"], case["n"], case["c"], case["off"], case["pad"]
+        tag = "case %d: metric=%d route=%s grid=%dx%d n=%d c=%d rlen=%d int_abs=%s %s %s off=%d pad=%d " \
+              "(PXSOM_FUZZ_SEED=%d)" % (case["i"], case["metric"], case["route"], xdim, ydim, n, c, case["rlen"],
+                                        case["int_abs"], case["dtype"], case["kind"], off, pad, SEED)
+        buf = torch.zeros((n, off + c + pad), dtype=TORCH_DT[case["dtype"]])
+        buf[:, off:off + c] = torch.from_numpy(case["x"])
+        x = buf.to(dev)[:, off:off + c]
+        w = torch.from_numpy(case["w0"].copy()).to(dev)
+        alpha, radius = (0.05, 0.01), default_radius_range(xdim, ydim)
+        order = torch.from_numpy(case["order"]).to(dev)
+        if case["route"] == "unsupported":
+            with pytest.raises(_capi.PxsomError):
+                som_device.train_online(x, w, xdim, ydim, case["rlen"], alpha, radius, order, int_abs=case["int_abs"],
+                                        metric=case["metric"])
+            continue
+        som_device.train_online(x, w, xdim, ydim, case["rlen"], alpha, radius, order, int_abs=case["int_abs"],
+                                metric=case["metric"])
+        want = mr.som_online(case["host"], case["w0"], xdim, ydim, case["rlen"], alpha, radius, case["order"],
+                             case["metric"], int_abs=case["int_abs"])
+        got = w.cpu().numpy()
+        assert np.array_equal(got.view(np.int64), want.view(np.int64)), tag + ": %d values differ" % int(
+            (got.view(np.int64) != want.view(np.int64)).sum())
