@@ -12,9 +12,11 @@ import subprocess
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 SO_PATH = os.path.join(_PKG, "libpxsom.so")
-SOURCES = ["pxsom_api.hip", "pxsom_assign.hip", "pxsom_assign_filter.hip", "pxsom_assign_filter_acc.hip", "pxsom_batch_step.hip", "pxsom_batch_step_wide.hip", "pxsom_train.hip",
-           "pxsom_pre.hip", "pxsom_sums.hip", "pxsom_comm.hip", "pxsom_metric.hip",
-           "pxsom_segmask.hip", "pxsom_cellquant.hip"]
+_CSRC = os.path.join(_PKG, "csrc")
+# every product source and header of csrc/ (nothing else lives there): a new file needs no entry here, and a header
+# cannot be left out of the digest
+SOURCES = sorted(f for f in os.listdir(_CSRC) if f.endswith(".hip"))
+HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h"))
 # per-file extra flags: the filter works on provably finite scores (see the file header)
 EXTRA_FLAGS = {"pxsom_assign_filter.hip": ["-ffinite-math-only"] + (
     ["-DSGB_VALU=" + os.environ["PXSOM_SGB_VALU"]] if "PXSOM_SGB_VALU" in os.environ else []) + (
@@ -31,8 +33,6 @@ def _hipcc() -> str:
     return exe
 
 
-HEADERS = ["pxsom_common.h", "pxsom_assign.h", "pxsom_wave.h", "pxsom_assign_filter_fast.h", "pxsom_batch_step.h", "pxsom_prep.h",
-           "pxsom_sums.h", "pxsom_assign_onepass.h", "pxsom_xch.h", "pxsom_metric.h"]
 STAMP_PATH = SO_PATH + ".srchash"
 
 

@@ -101,6 +101,19 @@ __host__ __device__ inline double filter_cut_abs(int c)
 constexpr float kTolFloor = 0x1p-100f;
 // the absolute coefficient every filter multiplies by |X'| + |W'|max: binary16 subnormal floor + the cuts
 __host__ __device__ inline double filter_tol_abs(int c) { return 2.5 * (0x1p-24 * sqrt((double)c) + filter_cut_abs(c)); }
+// The relative coefficient of the rigorous |filter - exact| bound, DESIGN.md "K7 error bound" -- THE rule: the training driver
+// forms every step's tolerance here, and the preparation kernel (pxsom_prep.h) writes the same expression out for the workspace it
+// fills (a call there reschedules that kernel; the two were compared bit for bit over every shape).  tol = 2 * 1.25 * E with E the sum of
+//   index packing 2^-(23 - idx_bits) (idx_bits low mantissa bits of a score replaced by the node index),
+//   the matrix unit's group additions accum_units * 2^-24 (filter_accum_units*; the cuts inside its groups: filter_tol_abs),
+//   split residual 2^-19, binary64 -> binary32 input rounding 2^-23,
+//   centred filter: + 2^-24, the rounding of x' = fl(x * scale - mu_s) (one fused operation).
+// (binary64, the terms in this order, rounded once to binary32: every caller must get the same bits)
+__host__ __device__ inline float filter_tol_rel(int idx_bits, double accum_units, bool centred)
+{
+    return (float)(2.5 * (ldexp(1.0, -(23 - idx_bits)) + accum_units * ldexp(1.0, -24) + ldexp(1.0, -19) + ldexp(1.0, -23) +
+                          (centred ? ldexp(1.0, -24) : 0.0)));
+}
 
 // Gain of the batch rule, 1 - (1 - alpha)^den for a whole den >= 1 (a window's row count), with q = 1 - alpha rounded once on
 // the host: binary exponentiation in plain binary64 products, low bit first -- no libm call, so orc_batch_gain

@@ -175,7 +175,7 @@ bool comm_fused_begin(pxsom_comm *c, int exchanges, size_t count, FusedXch *out)
     return true;
 }
 
-// used by the training loop (pxsom_train.hip)
+// used by the training loop (pxsom_batch_train.hip)
 int comm_allreduce_sum_f64(pxsom_comm *c, double *buf, size_t count, hipStream_t st)
 {
     if (c && c->p2p) return p2p_allreduce(c, buf, count, st);

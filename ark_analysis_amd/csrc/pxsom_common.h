@@ -39,6 +39,18 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 inline bool dtype_ok(int dtype) { return dtype == PXSOM_F32 || dtype == PXSOM_F64 || dtype == PXSOM_F16; }
 
+// a pixel matrix argument of entry point `fn`: n rows of c channels, leading dimension ldx
+inline int check_matrix(const char *fn, const void *x, int64_t n, int c, int64_t ldx, int dtype)
+{
+    if (n < 0) return fail(PXSOM_ERR_INVALID_ARG, "%s: n=%lld < 0", fn, (long long)n);
+    if (c < 1 || c > PXSOM_MAX_CHANNELS)
+        return fail(PXSOM_ERR_UNSUPPORTED, "%s: c=%d outside [1, %d]", fn, c, PXSOM_MAX_CHANNELS);
+    if (ldx < c) return fail(PXSOM_ERR_INVALID_ARG, "%s: ldx=%lld < c=%d", fn, (long long)ldx, c);
+    if (!dtype_ok(dtype)) return fail(PXSOM_ERR_UNSUPPORTED, "%s: dtype %d", fn, dtype);
+    if (n > 0 && !x) return fail(PXSOM_ERR_INVALID_ARG, "%s: null matrix", fn);
+    return PXSOM_OK;
+}
+
 // `return CALL<T>(static_cast<const T *>(ptr), ...)` for the pixel-matrix dtype (validated by the caller)
 #define PXSOM_DISPATCH_DTYPE(dtype, ptr, XP, CALL)                      \
     do {                                                                \

@@ -202,6 +202,8 @@ __device__ __forceinline__ void prep_body(const double *wl, int k, int c, Assign
         //   filter_accum_units * 2^-24 (the cuts inside its groups: tol_abs), split residual 2^-19,
         //   f64->f32 input rounding 2^-23;  tol = 2 * 1.25 * E
         //   centred filter: + 2^-24, the rounding of x' = fl(x * scale - mu_s) (one fused operation)
+        // (filter_tol_rel(idx_bits, filter_accum_units_for(c, 3, npk), center), pxsom_assign.h, written out: a call here evaluates
+        // the units ahead of the first term, and this kernel then comes out with another instruction schedule)
         const double coef = ldexp(1.0, -(23 - idx_bits)) +
                             filter_accum_units_for(c, 3, npk) * ldexp(1.0, -24) + ldexp(1.0, -19) + ldexp(1.0, -23) + (center ? ldexp(1.0, -24) : 0.0);
         hdr->tol_rel = (float)(2.5 * coef);

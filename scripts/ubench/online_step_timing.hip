@@ -1,8 +1,9 @@
 // Diagnosis: where does a step of the exact-online SOM kernel spend its cycles?  Includes the product
-// kernel source with PXSOM_STEP_TIMING (s_memtime deltas per segment, wave 0) and runs config-2-like
+// kernels (pxsom_online.h) with PXSOM_STEP_TIMING (s_memtime deltas per segment, wave 0) and runs config-2-like
 // input (C = 22, 10x10) for 200k steps.
 #define PXSOM_STEP_TIMING 1
-#include "../../ark_analysis_amd/csrc/pxsom_train.hip"
+#include "../../ark_analysis_amd/csrc/pxsom_online.h"
+template int pxsom::train_online<float>(PXSOM_ONLINE_ARGS(float));
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -28,7 +29,7 @@ int main()
         hipEvent_t e0, e1;
         hipEventCreate(&e0); hipEventCreate(&e1);
         hipEventRecord(e0, 0);
-        int rc = pxsom_train_online(dx, n, c, c, PXSOM_F32, dw, xdim, ydim, 1, 0.05, 0.01, 6.0, 0.0, dor, 0);
+        int rc = pxsom::train_online<float>(dx, n, c, c, dw, xdim, ydim, 1, 0.05, 0.01, 6.0, 0.0, dor, PXSOM_METRIC_EUCLIDEAN, 0, 0);
         hipEventRecord(e1, 0);
         hipDeviceSynchronize();
         float ms;

@@ -210,7 +210,7 @@ def test_bench_full_is_off_by_default(monkeypatch):
 
 def test_binary16_fixed_point_conversion_is_exact_for_every_finite_half():
     """The mean-table kernel turns a binary16 value into 2^-24 fixed point as bits(v + 1.5 * 2^28) - bits(1.5 * 2^28)
-    (csrc/pxsom_train.hip, cluster_sums_kernel): checked here for all 63 488 finite bit patterns, signed zeros and
+    (csrc/pxsom_sums.hip, cluster_sums_kernel): checked here for all 63 488 finite bit patterns, signed zeros and
     subnormals included; and the vector-wide Inf / NaN test ((bits & 0x7fff) + 0x0400 reaches bit 15) for all 65 536."""
     bits = np.arange(1 << 16, dtype=np.uint16)
     halves = bits.view(np.float16)

@@ -593,7 +593,7 @@ def test_fuzz_metric_assign():
 
 def online_metric_route(k, c):
     """The launch of pxsom_train_online_metric for k nodes x c channels, by the rule of train_online_metric_typed and
-    launch_online (csrc/pxsom_train.hip): "register" (CMAX > 0: rows in registers, codebook in registers), "lds" (CMAX 0,
+    launch_online (csrc/pxsom_online.h): "register" (CMAX > 0: rows in registers, codebook in registers), "lds" (CMAX 0,
     codebook in LDS beside the row ring), "in_place" (CMAX 0, the codebook does not fit: trained where it lies), or
     "unsupported" (more than 1024 nodes or channels: PXSOM_ERR_UNSUPPORTED)."""
     if k > 1024 or c > 1024:
