@@ -1,0 +1,129 @@
+"""The neighbourhood matrix and its k-means clusters (the reference's ``ark.analysis.neighborhood_analysis``).
+
+``create_neighborhood_matrix`` counts, per cell, the cells of each phenotype within ``distlim`` -- for every included FOV
+in one device launch over the centroid columns of the cell table (pxsom_neighbor_counts).  The reference
+reads one N x N distance matrix per FOV from ``dist_mat_dir``; here that directory is never opened.
+``generate_cluster_matrix_results`` runs k-means over the counts on the host and builds the reference's three tables; its
+first frame carries the ``kmeans_neighborhood`` column that ``utils.data_utils.generate_and_save_neighborhood_cluster_masks``
+consumes.
+
+Not mirrored: ``calc_dist_matrix`` and the ``.xr`` files (xarray is not a dependency here), the cell-distance analysis,
+the enrichment statistics, diversity and mixing scores, the k-means inertia / silhouette sweeps and the plots."""
+import warnings
+
+import numpy as np
+import pandas as pd
+
+from ..host_utils import verify_in_list
+from . import spatial_analysis_utils
+
+# the reference's column names (ark.settings)
+_FOV_ID, _CELL_LABEL, _CELL_TYPE, _KMEANS_CLUSTER = "fov", "label", "cell_meta_cluster", "kmeans_neighborhood"
+_CELL_SIZE, _CENTROIDS = "cell_size", ("centroid-0", "centroid-1")
+
+
+def create_neighborhood_matrix(all_data, dist_mat_dir=None, included_fovs=None, distlim=50, self_neighbor=False,
+                               fov_col=_FOV_ID, cell_label_col=_CELL_LABEL, cell_type_col=_CELL_TYPE, *,
+                               centroid_cols=_CENTROIDS):
+    """Per cell, the number of neighbours of each phenotype.
+
+    Args:
+        all_data (pandas.DataFrame): the cell table: FOV, label, phenotype and the two centroid columns.
+        dist_mat_dir: accepted for the reference's positional order and never opened.  The result equals the
+            reference's whenever the files there were written by ``calc_dist_matrix`` from this same table (what the
+            notebook does) and labels are unique within a FOV: the distances are then those of ``centroid_cols``.
+        included_fovs (list): FOVs to analyse (default: all).  The others keep rows of zeros, which are then dropped.
+        distlim: neighbours lie at float32 distance ``< distlim``, compared as numpy compares a float32 array with it.
+        self_neighbor (bool): count a cell (and any cell at float32 distance 0) as its own neighbour.
+        centroid_cols: the two centroid columns of ``all_data``.
+
+    Returns ``(counts, freqs)``: the three id columns, then one float64 column per phenotype in order of first
+    appearance; ``freqs`` divides a cell's counts by its number of neighbours.  Cells without any neighbour are dropped
+    (index reset), with a ``UserWarning`` when more than 5 % of all cells go.
+
+    Under a process group every rank computes the whole table: it is one launch, with nothing to exchange.
+    """
+    if included_fovs is None:
+        included_fovs = all_data[fov_col].unique()
+    verify_in_list(fov_names=included_fovs, unique_fovs=all_data[fov_col].unique())
+    missing = [c for c in centroid_cols if c not in all_data.columns]
+    if len(centroid_cols) != 2 or missing:
+        raise ValueError("create_neighborhood_matrix needs two centroid columns in all_data; missing: %s (pass "
+                         "centroid_cols=... if they are named differently)" % (missing or list(centroid_cols)))
+
+    id_cols = [fov_col, cell_label_col, cell_type_col]
+    ids = all_data[id_cols].reset_index(drop=True)
+    type_codes, type_names = pd.factorize(ids[cell_type_col].to_numpy(), sort=False)   # order of first appearance
+    if (type_codes < 0).any():
+        raise ValueError("create_neighborhood_matrix: column %r holds missing values" % cell_type_col)
+    n_cells, n_types = len(ids), len(type_names)
+
+    # rows of the included FOVs, FOV by FOV in table order: one segment each
+    fov_codes, fov_names = pd.factorize(ids[fov_col].to_numpy(), sort=False)
+    wanted = np.isin(fov_codes, np.flatnonzero(pd.Index(fov_names).isin(list(included_fovs))))
+    rows = np.flatnonzero(wanted)
+    rows = rows[np.argsort(fov_codes[rows], kind="stable")]
+    seg = np.concatenate([[0], np.cumsum(np.bincount(fov_codes[rows], minlength=len(fov_names)))])
+
+    counts = np.zeros((n_cells, n_types))
+    freqs = np.zeros((n_cells, n_types))
+    if len(rows):
+        xy = all_data[list(centroid_cols)].to_numpy(dtype=np.float64)[rows]
+        got = spatial_analysis_utils._neighbor_counts_device(xy, type_codes[rows], seg, n_types, distlim,
+                                                             bool(self_neighbor)).astype(np.float64)
+        counts[rows] = got
+        freqs[rows] = spatial_analysis_utils._freqs(got)
+
+    keep = counts.sum(axis=1) != 0
+    frames = []
+    for values in (counts, freqs):
+        frame = pd.concat([ids, pd.DataFrame(values, columns=pd.Index(list(type_names), dtype=object))], axis=1)
+        frames.append(frame.loc[keep].reset_index(drop=True))
+    if keep.sum() / n_cells < 0.95:
+        warnings.warn(UserWarning("More than 5% of cells have no neighbor within the provided radius and have been "
+                                  "omitted. We suggest increasing the distlim value to reduce the number of cells "
+                                  "excluded from analysis."))
+    return frames[0], frames[1]
+
+
+def generate_cluster_matrix_results(all_data, neighbor_mat, cluster_num, seed=42, excluded_channels=None,
+                                    included_fovs=None, cluster_label_col=_KMEANS_CLUSTER, fov_col=_FOV_ID,
+                                    cell_type_col=_CELL_TYPE, label_col=_CELL_LABEL, pre_channel_col=_CELL_SIZE,
+                                    post_channel_col=_CELL_LABEL):
+    """k-means over the neighbourhood matrix (on the host), then the reference's three tables:
+
+    - ``all_data`` restricted to the included FOVs and to cells of ``neighbor_mat``, with ``cluster_label_col`` attached;
+    - clusters x phenotypes: how many cells of each phenotype a cluster holds (index ``Cluster<k>``);
+    - clusters x channels: the mean of every column strictly between ``pre_channel_col`` and ``post_channel_col``
+      (less ``excluded_channels``) per cluster.
+
+    The labels come from ``spatial_analysis_utils.generate_cluster_labels``.
+    """
+    if included_fovs is None:
+        included_fovs = neighbor_mat[fov_col].unique()
+    verify_in_list(fov_names=included_fovs, unique_fovs=all_data[fov_col].unique())
+    if excluded_channels is not None:
+        verify_in_list(columns_to_exclude=excluded_channels, column_names=all_data.columns)
+    if cluster_num < 2:
+        raise ValueError("Invalid k provided for clustering")
+
+    mat = neighbor_mat[neighbor_mat[fov_col].isin(included_fovs)].copy()
+    mat[cluster_label_col] = spatial_analysis_utils.generate_cluster_labels(
+        mat.drop([fov_col, label_col, cell_type_col], axis=1), cluster_num, seed=seed)
+
+    clustered = all_data[all_data[fov_col].isin(included_fovs)].merge(
+        mat[[fov_col, label_col, cluster_label_col]], on=[fov_col, label_col])
+
+    sizes = clustered.groupby([cluster_label_col, cell_type_col]).size().reset_index(name="count")
+    per_type = sizes.pivot(index=cluster_label_col, columns=cell_type_col, values="count").fillna(0).astype(int)
+    per_type.index = ["Cluster" + str(c) for c in per_type.index]
+
+    first = np.where(clustered.columns == pre_channel_col)[0][0] + 1
+    last = np.where(clustered.columns == post_channel_col)[0][0]
+    label_at = np.where(clustered.columns == cluster_label_col)[0][0]
+    markers = clustered.iloc[:, list(range(first, last)) + [label_at]]
+    if excluded_channels is not None:
+        markers = markers.drop(excluded_channels, axis=1)
+    means = markers.groupby([cluster_label_col]).mean()
+    means.index = ["Cluster" + str(c) for c in means.index]
+    return clustered, per_type, means

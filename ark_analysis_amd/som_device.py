@@ -904,3 +904,85 @@ def cell_quantify(seg: torch.Tensor, img: torch.Tensor, keys: Optional[torch.Ten
                              _capi.stream_ptr())
     _capi.check(rc, "pxsom_cellquant")
     return out
+
+
+# ---- neighbourhood matrix (K13) -------------------------------------------------------------------------------------
+def _smallest_double(pred):
+    """The smallest double s in [0, +inf] with ``pred(s)`` for a monotone pred (False, ..., False, True, ..., True),
+    as its bit pattern; None when pred(+inf) is False.  Non-negative doubles order as their bit patterns do."""
+    def at(bits):
+        return bool(pred(np.array(bits, dtype=np.uint64).view(np.float64)[()]))
+    lo, hi = 0, 0x7FF0000000000000
+    if not at(hi):
+        return None
+    if at(lo):
+        return lo
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if at(mid):
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+def neighbor_thresholds(distlim) -> Tuple[float, float]:
+    """``(s_lim, s_zero)`` for pxsom_neighbor_counts: with ``d = float32(sqrt(s))`` the entry of the reference's distance
+    matrix for a squared distance s, ``d < distlim`` is ``s < s_lim`` and ``d == 0`` is ``s <= s_zero``, exactly --
+    sqrt and the cast to float32 are correctly rounded and monotone, so each test flips at one double, found here by
+    bisection over the bit patterns.  ``distlim`` compares in the dtype numpy compares a float32 array with it in
+    (``np.result_type(np.float32, distlim)``: a Python scalar in float32, an ``np.float64`` in float64)."""
+    lim = np.result_type(np.float32, distlim).type(distlim)
+
+    def d32(s):
+        with np.errstate(over="ignore"):
+            return np.float32(np.sqrt(s))
+    at_lim = _smallest_double(lambda s: d32(s) >= lim)
+    above_zero = _smallest_double(lambda s: d32(s) > 0)
+    as_double = lambda bits: float(np.array(bits, dtype=np.uint64).view(np.float64)[()])  # noqa: E731
+    # a NaN distlim is below nothing: s < 0 never holds
+    return (0.0 if at_lim is None else as_double(at_lim)), as_double(above_zero - 1)
+
+
+def neighbor_counts(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_types: int, distlim,
+                    self_neighbor: bool = False) -> torch.Tensor:
+    """pxsom_neighbor_counts: ``counts[i, t]`` (``[n, n_types]`` int32, HBM) = how many cells j of cell i's FOV with
+    ``types[j] == t`` have ``float32(dist(i, j)) < distlim`` (and ``!= 0`` unless ``self_neighbor``), dist the binary64
+    Euclidean distance of the centroids ``xy`` [n, 2] -- the reference's compute_neighbor_counts over calc_dist_matrix's
+    matrix, which is never built.  ``types`` [n] int32 / int64 in [0, n_types); ``seg`` [F + 1] int64 offsets (FOV f is
+    rows seg[f] .. seg[f + 1], seg[0] = 0, seg[F] = n, empty FOVs allowed).  Rows come in and go out in the caller's
+    order: the sort by type inside each FOV that the kernel wants is done here."""
+    if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float64 or not xy.is_cuda:
+        raise ValueError("xy must be an [n, 2] float64 HBM tensor")
+    n, dev = xy.shape[0], xy.device
+    if types.dim() != 1 or types.shape[0] != n or types.dtype not in (torch.int32, torch.int64) or types.device != dev:
+        raise ValueError("types must be an [n] int32 / int64 HBM vector on xy's device")
+    if seg.dim() != 1 or seg.numel() < 1 or seg.dtype != torch.int64 or seg.device != dev:
+        raise ValueError("seg must be an [F + 1] int64 HBM vector on xy's device")
+    n_types = operator.index(n_types)
+    if n_types < 1:
+        raise ValueError("n_types must be at least 1")
+    s_lim, s_zero = neighbor_thresholds(distlim)
+    seg = seg.contiguous()
+    n_fovs = seg.numel() - 1
+    ok = torch.stack([seg[0] == 0, seg[-1] == n, (seg[1:] >= seg[:-1]).all(),
+                      ((types >= 0) & (types < n_types)).all()]).cpu()
+    if not bool(ok[:3].all()):
+        raise ValueError("seg must be non-decreasing offsets from 0 to n")
+    if not bool(ok[3]):
+        raise ValueError("types must lie in [0, n_types)")
+    counts = torch.empty((n, n_types), dtype=torch.int32, device=dev)
+    if n == 0:
+        return counts
+    rows = torch.arange(n, device=dev)
+    fov = torch.searchsorted(seg[1:], rows, right=True)
+    order = torch.argsort(fov * n_types + types.to(torch.int64), stable=True)
+    xy_s = xy[order].contiguous()
+    types_s = types[order].to(torch.int32).contiguous()
+    sorted_counts = torch.empty_like(counts)
+    rc = _capi.lib().pxsom_neighbor_counts(xy_s.data_ptr(), types_s.data_ptr(), seg.data_ptr(), n_fovs, n, n_types,
+                                           s_lim, s_zero, 1 if self_neighbor else 0, sorted_counts.data_ptr(),
+                                           _capi.stream_ptr())
+    _capi.check(rc, "pxsom_neighbor_counts")
+    counts[order] = sorted_counts
+    return counts

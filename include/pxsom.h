@@ -552,6 +552,27 @@ int pxsom_cellquant(const void *seg_dev, int seg_dtype, int64_t ld, const void *
                     int64_t *count_dev, int64_t *sums_dev, int32_t *bbox_dev, double *values_dev, int32_t *nuc_out_dev,
                     void *workspace_dev, size_t workspace_bytes, int flags, void *stream);
 
+/* ---- neighbourhood matrix: per-cell neighbour counts by phenotype, from the centroids (K13) -------------------------
+ * reference: ark/analysis/spatial_analysis_utils.py calc_dist_matrix (cdist(...).astype(float32), one N x N matrix per
+ * FOV) and compute_neighbor_counts (dist < distlim, dist == 0 removed unless self_neighbor, one-hot dot).  One
+ * stream-ordered launch covers the cohort and the N x N matrix is never built.
+ *   xy_dev   [n, 2] binary64 centroids, 16-byte aligned
+ *   type_dev [n] int32 in [0, n_types); WITHIN each FOV the rows MUST be sorted by type, ascending (not checked here: the
+ *            Python wrapper sorts and restores the caller's order)
+ *   seg_dev  [n_fovs + 1] int64 offsets, non-decreasing, seg[0] = 0, seg[n_fovs] = n: FOV f is rows seg[f] .. seg[f + 1];
+ *            an empty FOV is allowed
+ * For cells i and j of one FOV (j = i included): s = fl(fl(dx * dx) + fl(dy * dy)) in binary64 without contraction; j
+ * is a neighbour of i when s < s_lim and (self_neighbor or s > s_zero).  counts_dev[i * n_types + type[j]] (int32) is
+ * the number of such j; every entry of counts_dev [n, n_types] is written (the caller need not clear it).  With s_lim the
+ * smallest double whose float32(sqrt(s)) >= distlim and s_zero the largest whose float32(sqrt(s)) == 0 the test is
+ * float32(sqrt(s)) < distlim and != 0 exactly: sqrt and the cast are correctly rounded and monotone.
+ * No workspace.  Offsets are clamped to [0, n] and a type that is out of range or out of order is not stored, so bad
+ * device-side input gives wrong rows, never a write outside counts_dev.  Bad sizes, flag, NaN thresholds or null /
+ * misaligned pointers: PXSOM_ERR_INVALID_ARG before any HIP call. */
+int pxsom_neighbor_counts(const double *xy_dev, const int32_t *type_dev, const int64_t *seg_dev, int64_t n_fovs,
+                          int64_t n, int n_types, double s_lim, double s_zero, int self_neighbor, int32_t *counts_dev,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
