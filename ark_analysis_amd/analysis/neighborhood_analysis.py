@@ -7,8 +7,10 @@ reads one N x N distance matrix per FOV from ``dist_mat_dir``; here that directo
 first frame carries the ``kmeans_neighborhood`` column that ``utils.data_utils.generate_and_save_neighborhood_cluster_masks``
 consumes.
 
-Not mirrored: ``calc_dist_matrix`` and the ``.xr`` files (xarray is not a dependency here), the cell-distance analysis,
-the enrichment statistics, diversity and mixing scores, the k-means inertia / silhouette sweeps and the plots."""
+The notebook's other two steps, the cell-distance and the diversity analysis, are in ``cell_neighborhood_stats``.
+
+Not mirrored: ``calc_dist_matrix`` and the ``.xr`` files (xarray is not a dependency here), the enrichment statistics,
+the mixing scores, the k-means inertia / silhouette sweeps and the plots."""
 import warnings
 
 import numpy as np

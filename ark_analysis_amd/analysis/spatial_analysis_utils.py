@@ -2,7 +2,8 @@
 
 ``compute_neighbor_counts`` takes a FOV's centroids where the reference takes its distance matrix: the counts come from
 one pxsom_neighbor_counts launch and the N x N matrix is never built.  Not mirrored: ``calc_dist_matrix``
-and its ``.xr`` files (xarray is not a dependency here), the cell-distance features, the enrichment statistics
+and its ``.xr`` files (xarray is not a dependency here), the distance-feature columns
+(``append_distance_features_to_dataset``; the cell-distance analysis is ``cell_neighborhood_stats``), the enrichment statistics
 (``compute_close_cell_num``, ``calculate_enrichment_stats``), the k-means inertia / silhouette sweeps and everything that
 plots."""
 import numpy as np

@@ -986,3 +986,61 @@ def neighbor_counts(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_
     _capi.check(rc, "pxsom_neighbor_counts")
     counts[order] = sorted_counts
     return counts
+
+
+# ---- cell-distance analysis (K14) -----------------------------------------------------------------------------------
+NEAREST_MAX_K = 32      # pxsom_nearest_type_means keeps the k smallest squared distances in registers
+_S_ZERO = None
+
+
+def _nearest_s_zero() -> float:
+    """neighbor_thresholds' s_zero (it does not depend on distlim), bisected once per process."""
+    global _S_ZERO
+    if _S_ZERO is None:
+        _S_ZERO = neighbor_thresholds(1)[1]
+    return _S_ZERO
+
+
+def nearest_type_means(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_types: int, k: int) -> torch.Tensor:
+    """pxsom_nearest_type_means: ``means[i, t]`` (``[n, n_types]`` float32, HBM) = the mean of the k smallest non-zero
+    float32 distances from cell i to the cells j of its FOV with ``types[j] == t``, NaN when fewer than k are non-zero
+    -- the reference's calculate_mean_distance_to_cell_type over calc_dist_matrix's matrix, which is never built, bit for
+    bit (float32 sum in numpy's pairwise order).  Arguments as for :func:`neighbor_counts`; ``1 <= k <= 32``.  Rows come
+    in and go out in the caller's order: the sort by type inside each FOV that the kernel wants is done here."""
+    if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float64 or not xy.is_cuda:
+        raise ValueError("xy must be an [n, 2] float64 HBM tensor")
+    n, dev = xy.shape[0], xy.device
+    if types.dim() != 1 or types.shape[0] != n or types.dtype not in (torch.int32, torch.int64) or types.device != dev:
+        raise ValueError("types must be an [n] int32 / int64 HBM vector on xy's device")
+    if seg.dim() != 1 or seg.numel() < 1 or seg.dtype != torch.int64 or seg.device != dev:
+        raise ValueError("seg must be an [F + 1] int64 HBM vector on xy's device")
+    n_types = operator.index(n_types)
+    if n_types < 1:
+        raise ValueError("n_types must be at least 1")
+    k = operator.index(k)
+    if not 1 <= k <= NEAREST_MAX_K:
+        raise ValueError("k must lie in 1 .. %d (the device route keeps the k nearest in registers), got %d"
+                         % (NEAREST_MAX_K, k))
+    s_zero = _nearest_s_zero()
+    seg = seg.contiguous()
+    n_fovs = seg.numel() - 1
+    ok = torch.stack([seg[0] == 0, seg[-1] == n, (seg[1:] >= seg[:-1]).all(),
+                      ((types >= 0) & (types < n_types)).all()]).cpu()
+    if not bool(ok[:3].all()):
+        raise ValueError("seg must be non-decreasing offsets from 0 to n")
+    if not bool(ok[3]):
+        raise ValueError("types must lie in [0, n_types)")
+    means = torch.empty((n, n_types), dtype=torch.float32, device=dev)
+    if n == 0:
+        return means
+    rows = torch.arange(n, device=dev)
+    fov = torch.searchsorted(seg[1:], rows, right=True)
+    order = torch.argsort(fov * n_types + types.to(torch.int64), stable=True)
+    xy_s = xy[order].contiguous()
+    types_s = types[order].to(torch.int32).contiguous()
+    sorted_means = torch.empty_like(means)
+    rc = _capi.lib().pxsom_nearest_type_means(xy_s.data_ptr(), types_s.data_ptr(), seg.data_ptr(), n_fovs, n, n_types, k,
+                                              s_zero, sorted_means.data_ptr(), _capi.stream_ptr())
+    _capi.check(rc, "pxsom_nearest_type_means")
+    means[order] = sorted_means
+    return means

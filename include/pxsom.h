@@ -573,6 +573,26 @@ int pxsom_neighbor_counts(const double *xy_dev, const int32_t *type_dev, const i
                           int64_t n, int n_types, double s_lim, double s_zero, int self_neighbor, int32_t *counts_dev,
                           void *stream);
 
+/* ---- cell-distance analysis: per cell, the mean distance to its k nearest cells of every phenotype (K14) -------------
+ * reference: ark/analysis/cell_neighborhood_stats.py calculate_mean_distance_to_cell_type over calc_dist_matrix's float32
+ * matrix (the columns of one phenotype, where(dist > 0), np.sort per row, [:, :k].mean(axis=1)).  One stream-ordered
+ * launch covers the cohort and the N x N matrix is never built.
+ *   xy_dev, type_dev, seg_dev, n_fovs, n, n_types: as for pxsom_neighbor_counts (rows of a FOV sorted by type)
+ *   k        1 .. 32 (the device route's limit: the k smallest live in registers)
+ *   s_zero   the largest double whose float32(sqrt(s)) == 0 (som_device.neighbor_thresholds)
+ * For cell i and type t take every j of i's FOV with type[j] == t (j = i included), s = fl(fl(dx * dx) + fl(dy * dy)) in
+ * binary64 without contraction, and keep those with s > s_zero.  Fewer than k kept: means_dev[i * n_types + t] = NaN.
+ * Otherwise the k smallest s, ascending, each mapped to float32(sqrt(s)) (sqrt correctly rounded in binary64, then
+ * rounded to float32), are summed in float32 in the order numpy's pairwise row reduction uses -- a fold from 0 for
+ * k < 8; else eight strided accumulators over the first k - k % 8 terms, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the
+ * remaining terms in order -- and divided by float32(k).  Every entry of means_dev [n, n_types] (float32) is written
+ * (the caller need not clear it); a row no FOV holds is NaN.
+ * No workspace.  Offsets are clamped to [0, n] and a type that is out of range or out of order is not stored, so bad
+ * device-side input gives wrong rows, never a write outside means_dev.  Bad sizes, k outside 1 .. 32, a NaN s_zero or
+ * null / misaligned pointers: PXSOM_ERR_INVALID_ARG before any HIP call. */
+int pxsom_nearest_type_means(const double *xy_dev, const int32_t *type_dev, const int64_t *seg_dev, int64_t n_fovs,
+                             int64_t n, int n_types, int k, double s_zero, float *means_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
