@@ -16,6 +16,110 @@
 #include "pxsom_metric.h"
 #include "pxsom_wave.h"
 
+// ------------------------------------------------------------------------------------------------
+// The route of a shape: which kernel, how many threads, which chunk, how much LDS, codebook in place or not.  Decided
+// here and only here -- the launchers below take the plan as it is, and pxsom_train_online_route reports it.
+// Each table row is (node bound, channel bound, kernel form); the first row whose two bounds hold wins.
+// ------------------------------------------------------------------------------------------------
+// Euclidean, several lanes per node -- (K <=, c <=, CH channels per lane, L lanes per node): fewer binary64 instructions
+// per wave per step on small maps; the 16 / 20 / 26 x 4 rows are the cell SOM's wide rows (~100 cluster-count features)
+// on maps up to 128 nodes, 4 lanes per node in a 512-thread workgroup (two waves per SIMD)
+#define PXSOM_ONLINE_SPLIT_ROUTES(X)                                             \
+    X(64, 16, 4, 4) X(64, 24, 6, 4) X(64, 40, 10, 4)                             \
+    X(128, 8, 4, 2) X(128, 16, 8, 2) X(128, 24, 12, 2) X(128, 40, 20, 2)         \
+    X(128, 64, 16, 4) X(128, 80, 20, 4) X(128, 104, 26, 4)
+// Euclidean, thread per node -- (K <=, c <=, CMAX, MAXT).  <= 256 nodes: 4 waves at most, the whole register file is
+// available per thread (104: one wave per SIMD, 512 registers); <= 512 nodes (config 5's 20 x 20 map): two waves per
+// SIMD, 256 registers per thread; more nodes or wider rows: 128 VGPRs per thread, the codebook stays out of registers
+#define PXSOM_ONLINE_NODE_ROUTES(X)                                                                   \
+    X(256, 8, 8, 256) X(256, 16, 16, 256) X(256, 24, 24, 256) X(256, 40, 40, 256) X(256, 64, 64, 256) \
+    X(256, 104, 104, 256) X(256, PXSOM_MAX_CHANNELS, 0, 256)                                          \
+    X(512, 8, 8, 512) X(512, 16, 16, 512) X(512, 24, 24, 512) X(512, 40, 40, 512)                     \
+    X(PXSOM_MAX_NODES, PXSOM_MAX_CHANNELS, 0, 1024)
+// Manhattan, Chebyshev, cosine: thread per node for every shape (the split kernel's several lanes per node would sum a
+// node's channels out of the oracle's order); fewer register widths than the Euclidean route -- pad slots add exact zeros
+#define PXSOM_ONLINE_METRIC_ROUTES(X)                                                                  \
+    X(256, 8, 8, 256) X(256, 24, 24, 256) X(256, 40, 40, 256) X(256, 64, 64, 256)                      \
+    X(256, PXSOM_MAX_CHANNELS, 0, 256) X(512, 16, 16, 512) X(512, 40, 40, 512)                         \
+    X(PXSOM_MAX_NODES, PXSOM_MAX_CHANNELS, 0, 1024)
+
+namespace pxsom {
+
+// the record of pxsom_train_online_route, field for field (include/pxsom.h)
+struct OnlinePlan {
+    int family;     // PXSOM_ONLINE_LANES_PER_NODE / PXSOM_ONLINE_THREAD_PER_NODE
+    int width;      // CH (channels per lane) / CMAX (register width; 0: the codebook is not in registers)
+    int span;       // L (lanes per node) / MAXT (the kernel's thread bound)
+    int in_place;   // CMAX 0 only: the codebook does not fit the LDS beside the row ring and is trained where it lies
+    int threads;
+    int chunk;      // steps whose rows are gathered ahead together
+    int lds_bytes;
+};
+
+// K nodes x c channels (both validated by the caller) under `metric`.  Host arithmetic only.
+inline int plan_online(int K, int c, int metric, OnlinePlan *p)
+{
+    *p = OnlinePlan{-1, 0, 0, 0, 0, 0, 0};
+#define PXSOM_ROUTE(KB, CB, W, S)                           \
+    if (p->family < 0 && K <= (KB) && c <= (CB)) {          \
+        p->family = family;                                 \
+        p->width = (W);                                     \
+        p->span = (S);                                      \
+    }
+    int family = PXSOM_ONLINE_LANES_PER_NODE;
+    if (metric == PXSOM_METRIC_EUCLIDEAN) {
+        PXSOM_ONLINE_SPLIT_ROUTES(PXSOM_ROUTE)
+    }
+    family = PXSOM_ONLINE_THREAD_PER_NODE;
+    if (metric == PXSOM_METRIC_EUCLIDEAN) {
+        PXSOM_ONLINE_NODE_ROUTES(PXSOM_ROUTE)
+    } else {
+        PXSOM_ONLINE_METRIC_ROUTES(PXSOM_ROUTE)
+    }
+#undef PXSOM_ROUTE
+    if (p->family < 0)
+        return fail(PXSOM_ERR_UNSUPPORTED, "pxsom_train_online: %d nodes x %d channels: no kernel", K, c);
+    if (p->family == PXSOM_ONLINE_LANES_PER_NODE) {
+        const int CH = p->width, L = p->span;
+        const int bd = ((K * L + 63) / 64) * 64;
+        int chunk = 64;
+        while ((chunk * c + bd - 1) / bd > 16) chunk >>= 1;  // gather registers per thread
+        p->threads = bd;
+        p->chunk = chunk;
+        p->lds_bytes = (int)((size_t)2 * chunk * CH * L * 8 + (3 * 128 + 8) * 8 + (size_t)chunk * 8 +
+                             (size_t)2 * chunk * 8 + (size_t)(CH * L + 2) * 8);
+        return PXSOM_OK;
+    }
+    const int CMAX = p->width;
+    const int bd = ((K + 63) / 64) * 64;
+    const int nwv = bd / 64;
+    const int cs = CMAX > 0 ? CMAX : c;
+    // LDS besides the row ring: the codebook (CMAX == 0, when it fits) + per-wave exchange + learning rates
+    auto plan = [&](bool codebook_in_lds, int *chunk_out) -> size_t {
+        const size_t fixed = (codebook_in_lds ? (size_t)c * K * 8 : 0) + (size_t)2 * nwv * 8 + (size_t)2 * nwv * 4 +
+                             (size_t)nwv * 8 + 2 * 64 * 8 + 64;
+        int chunk = 64;
+        while (chunk > 8 && fixed + (size_t)2 * chunk * cs * 8 > 150 * 1024) chunk >>= 1;
+        while ((chunk * c + bd - 1) / bd > 16) chunk >>= 1;  // gather registers per thread
+        *chunk_out = chunk;
+        return fixed + (size_t)2 * chunk * cs * 8;
+    };
+    int chunk = 0;
+    size_t lds = plan(CMAX == 0, &chunk);
+    if (CMAX == 0 && (chunk < 1 || lds > 160 * 1024)) {  // the codebook does not fit beside the ring: train it where it lies
+        p->in_place = 1;
+        lds = plan(false, &chunk);
+    }
+    if (chunk < 1 || lds > 160 * 1024)
+        return fail(PXSOM_ERR_UNSUPPORTED, "pxsom_train_online: %d nodes x %d channels: no LDS for the row ring", K, c);
+    p->threads = bd;
+    p->chunk = chunk;
+    p->lds_bytes = (int)lds;
+    return PXSOM_OK;
+}
+
+}  // namespace pxsom
+
 namespace {
 
 using pxsom::dpp_f64;
@@ -620,150 +724,69 @@ __global__ __launch_bounds__(CH * L > 40 ? 512 : 256) void som_online_split_kern
 
 #pragma clang fp contract(fast)
 
-template <typename T, int CMAX, int MAXT, int M = PXSOM_METRIC_EUCLIDEAN>
-int launch_online(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen, double a0,
-                  double a1, double r0, double r1, const int64_t *order, int flags, hipStream_t st)
-{
-    const int K = xdim * ydim;
-    const int bd = ((K + 63) / 64) * 64;
-    const int nwv = bd / 64;
-    const int cs = CMAX > 0 ? CMAX : c;
-    // LDS besides the row ring: the codebook (CMAX == 0, when it fits) + per-wave exchange + learning rates
-    auto plan = [&](bool codebook_in_lds, int *chunk_out) -> size_t {
-        const size_t fixed = (codebook_in_lds ? (size_t)c * K * 8 : 0) + (size_t)2 * nwv * 8 + (size_t)2 * nwv * 4 +
-                             (size_t)nwv * 8 + 2 * 64 * 8 + 64;
-        int chunk = 64;
-        while (chunk > 8 && fixed + (size_t)2 * chunk * cs * 8 > 150 * 1024) chunk >>= 1;
-        while ((chunk * c + bd - 1) / bd > 16) chunk >>= 1;  // gather registers per thread
-        *chunk_out = chunk;
-        return fixed + (size_t)2 * chunk * cs * 8;
-    };
-    int chunk = 0;
-    size_t lds = plan(CMAX == 0, &chunk);
-    bool in_place = false;
-    if constexpr (CMAX == 0) {
-        if (chunk < 1 || lds > 160 * 1024) {   // the codebook does not fit beside the ring: train it where it lies
-            in_place = true;
-            lds = plan(false, &chunk);
-        }
-    }
-    if (chunk < 1 || lds > 160 * 1024)
-        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_train_online: %d nodes x %d channels: no LDS for the row ring", K, c);
-    auto launch = [&](auto kern) -> int {
-        PXSOM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(1), dim3(bd), lds, st, x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1,
-                           order, chunk, flags);
-        PXSOM_LAUNCH_CHECK("som_online_kernel");
-        return PXSOM_OK;
-    };
-    if constexpr (CMAX == 0) {
-        if (in_place) return launch(som_online_kernel<T, CMAX, MAXT, true, M>);
-    }
-    return launch(som_online_kernel<T, CMAX, MAXT, false, M>);
-}
+// the arguments of one training run, as the kernels take them
+template <typename T>
+struct OnlineArgs {
+    const T *x;
+    int64_t n;
+    int c;
+    int64_t ldx;
+    double *w;
+    int xdim, ydim, rlen;
+    double a0, a1, r0, r1;
+    const int64_t *order;
+    int flags;
+    hipStream_t st;
+};
 
-template <typename T, int CH, int L>
-int launch_online_split(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen,
-                        double a0, double a1, double r0, double r1, const int64_t *order, int flags, hipStream_t st)
+// Both launchers take the plan as it is (pxsom::plan_online): threads, chunk, LDS bytes and the in-place decision are
+// computed there and nowhere else.
+template <typename T, typename Kernel>
+int launch_planned(Kernel kern, const char *name, const pxsom::OnlinePlan &p, const OnlineArgs<T> &a, bool raise_lds)
 {
-    const int K = xdim * ydim;
-    const int bd = ((K * L + 63) / 64) * 64;
-    int chunk = 64;
-    while ((chunk * c + bd - 1) / bd > 16) chunk >>= 1;  // gather registers per thread
-    const size_t lds = (size_t)2 * chunk * CH * L * 8 + (3 * 128 + 8) * 8 + (size_t)chunk * 8 +
-                       (size_t)2 * chunk * 8 + (size_t)(CH * L + 2) * 8;
-    auto kern = som_online_split_kernel<T, CH, L>;
-    if (lds > 48 * 1024)
+    if (raise_lds)
         PXSOM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(bd), lds, st, x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1,
-                       order, chunk, flags);
-    PXSOM_LAUNCH_CHECK("som_online_split_kernel");
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes));
+    hipLaunchKernelGGL(kern, dim3(1), dim3(p.threads), (size_t)p.lds_bytes, a.st, a.x, a.n, a.c, a.ldx, a.w, a.xdim, a.ydim,
+                       a.rlen, a.a0, a.a1, a.r0, a.r1, a.order, p.chunk, a.flags);
+    PXSOM_LAUNCH_CHECK(name);
     return PXSOM_OK;
 }
 
-template <typename T>
-int train_online_typed(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen,
-                       double a0, double a1, double r0, double r1, const int64_t *order, int flags, hipStream_t st)
+template <typename T, int CMAX, int MAXT, int M>
+int launch_online(const pxsom::OnlinePlan &p, const OnlineArgs<T> &a)
 {
-#define PXSOM_ONLINE(CM, MT) \
-    return launch_online<T, CM, MT>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st)
-#define PXSOM_ONLINE_SPLIT(CH, L) \
-    return launch_online_split<T, CH, L>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st)
-    // small maps: several lanes per node (fewer binary64 instructions per wave per step)
-    if (xdim * ydim <= 64 && c <= 40) {
-        if (c <= 16) PXSOM_ONLINE_SPLIT(4, 4);
-        if (c <= 24) PXSOM_ONLINE_SPLIT(6, 4);
-        PXSOM_ONLINE_SPLIT(10, 4);
+    if constexpr (CMAX == 0) {
+        if (p.in_place) return launch_planned(som_online_kernel<T, CMAX, MAXT, true, M>, "som_online_kernel", p, a, true);
     }
-    if (xdim * ydim <= 128 && c <= 40) {
-        if (c <= 8) PXSOM_ONLINE_SPLIT(4, 2);
-        if (c <= 16) PXSOM_ONLINE_SPLIT(8, 2);
-        if (c <= 24) PXSOM_ONLINE_SPLIT(12, 2);
-        PXSOM_ONLINE_SPLIT(20, 2);
-    }
-    // wide rows (cell SOM: ~100 cluster-count features) on maps up to 128 nodes: 4 lanes per node in a
-    // 512-thread workgroup (two waves per SIMD)
-    if (xdim * ydim <= 128 && c <= 104) {
-        if (c <= 64) PXSOM_ONLINE_SPLIT(16, 4);
-        if (c <= 80) PXSOM_ONLINE_SPLIT(20, 4);
-        PXSOM_ONLINE_SPLIT(26, 4);
-    }
-#undef PXSOM_ONLINE_SPLIT
-    // <= 256 nodes: 4 waves at most, the whole register file is available per thread
-    if (xdim * ydim <= 256) {
-        if (c <= 8) PXSOM_ONLINE(8, 256);
-        if (c <= 16) PXSOM_ONLINE(16, 256);
-        if (c <= 24) PXSOM_ONLINE(24, 256);
-        if (c <= 40) PXSOM_ONLINE(40, 256);
-        if (c <= 64) PXSOM_ONLINE(64, 256);
-        if (c <= 104) PXSOM_ONLINE(104, 256);   // cell SOM: ~100 cluster-count features (one wave per SIMD: 512 registers)
-        PXSOM_ONLINE(0, 256);
-    }
-    // <= 512 nodes (config 5's 20 x 20 map): two waves per SIMD, 256 registers per thread
-    if (xdim * ydim <= 512) {
-        if (c <= 8) PXSOM_ONLINE(8, 512);
-        if (c <= 16) PXSOM_ONLINE(16, 512);
-        if (c <= 24) PXSOM_ONLINE(24, 512);
-        if (c <= 40) PXSOM_ONLINE(40, 512);
-    }
-    PXSOM_ONLINE(0, 1024);  // more nodes or wider rows: 128 VGPRs per thread, codebook stays in LDS
-#undef PXSOM_ONLINE
+    return launch_planned(som_online_kernel<T, CMAX, MAXT, false, M>, "som_online_kernel", p, a, true);
 }
 
-// Manhattan, Chebyshev, cosine: thread <-> node for every shape (the split kernel's several lanes per node would sum a
-// node's channels out of the oracle's order); fewer register widths than the Euclidean route -- pad slots add exact zeros
+template <typename T, int CH, int L>
+int launch_online_split(const pxsom::OnlinePlan &p, const OnlineArgs<T> &a)
+{
+    return launch_planned(som_online_split_kernel<T, CH, L>, "som_online_split_kernel", p, a, p.lds_bytes > 48 * 1024);
+}
+
+// The kernel of a plan: one instantiation per row of the route tables (the rows name CH x L or CMAX x MAXT once each).
 template <typename T, int M>
-int train_online_metric_typed(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen,
-                              double a0, double a1, double r0, double r1, const int64_t *order, int flags, hipStream_t st)
+int launch_online_plan(const pxsom::OnlinePlan &p, const OnlineArgs<T> &a)
 {
-#define PXSOM_ONLINE_M(CM, MT) \
-    return launch_online<T, CM, MT, M>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st)
-    if (xdim * ydim <= 256) {
-        if (c <= 8) PXSOM_ONLINE_M(8, 256);
-        if (c <= 24) PXSOM_ONLINE_M(24, 256);
-        if (c <= 40) PXSOM_ONLINE_M(40, 256);
-        if (c <= 64) PXSOM_ONLINE_M(64, 256);
-        PXSOM_ONLINE_M(0, 256);
+    if constexpr (M == PXSOM_METRIC_EUCLIDEAN) {
+#define PXSOM_ROUTE(KB, CB, CH, L) \
+    if (p.family == PXSOM_ONLINE_LANES_PER_NODE && p.width == CH && p.span == L) return launch_online_split<T, CH, L>(p, a);
+        PXSOM_ONLINE_SPLIT_ROUTES(PXSOM_ROUTE)
+#undef PXSOM_ROUTE
     }
-    if (xdim * ydim <= 512) {
-        if (c <= 16) PXSOM_ONLINE_M(16, 512);
-        if (c <= 40) PXSOM_ONLINE_M(40, 512);
+#define PXSOM_ROUTE(KB, CB, CM, MT) \
+    if (p.family == PXSOM_ONLINE_THREAD_PER_NODE && p.width == CM && p.span == MT) return launch_online<T, CM, MT, M>(p, a);
+    if constexpr (M == PXSOM_METRIC_EUCLIDEAN) {
+        PXSOM_ONLINE_NODE_ROUTES(PXSOM_ROUTE)
+    } else {
+        PXSOM_ONLINE_METRIC_ROUTES(PXSOM_ROUTE)
     }
-    PXSOM_ONLINE_M(0, 1024);
-#undef PXSOM_ONLINE_M
-}
-
-template <typename T>
-int train_online_metric(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen, double a0,
-                        double a1, double r0, double r1, const int64_t *order, int metric, int flags, hipStream_t st)
-{
-    if (metric == PXSOM_METRIC_MANHATTAN)
-        return train_online_metric_typed<T, PXSOM_METRIC_MANHATTAN>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st);
-    if (metric == PXSOM_METRIC_CHEBYSHEV)
-        return train_online_metric_typed<T, PXSOM_METRIC_CHEBYSHEV>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st);
-    return train_online_metric_typed<T, PXSOM_METRIC_COSINE>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st);
+#undef PXSOM_ROUTE
+    return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_train_online: no kernel for plan %d / %d / %d", p.family, p.width, p.span);
 }
 
 }  // namespace
@@ -776,9 +799,16 @@ template <typename T>
 int train_online(const T *x, int64_t n, int c, int64_t ldx, double *w, int xdim, int ydim, int rlen, double a0, double a1,
                  double r0, double r1, const int64_t *order, int metric, int flags, hipStream_t st)
 {
-    if (metric == PXSOM_METRIC_EUCLIDEAN)
-        return train_online_typed<T>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st);
-    return train_online_metric<T>(x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, metric, flags, st);
+    OnlinePlan p;
+    const int rc = plan_online(xdim * ydim, c, metric, &p);
+    if (rc) return rc;
+    const OnlineArgs<T> a{x, n, c, ldx, w, xdim, ydim, rlen, a0, a1, r0, r1, order, flags, st};
+    switch (metric) {
+    case PXSOM_METRIC_MANHATTAN: return launch_online_plan<T, PXSOM_METRIC_MANHATTAN>(p, a);
+    case PXSOM_METRIC_CHEBYSHEV: return launch_online_plan<T, PXSOM_METRIC_CHEBYSHEV>(p, a);
+    case PXSOM_METRIC_COSINE: return launch_online_plan<T, PXSOM_METRIC_COSINE>(p, a);
+    default: return launch_online_plan<T, PXSOM_METRIC_EUCLIDEAN>(p, a);
+    }
 }
 
 // `template int pxsom::train_online<T>(PXSOM_ONLINE_ARGS(T));` in the unit of row type T and nowhere else

@@ -182,6 +182,33 @@ def batch_train_fused_route(x: torch.Tensor, xdim: int, ydim: int, schedule) -> 
                                                           resolve(schedule).phases))
 
 
+ONLINE_ROUTE_FIELDS = ("family", "width", "span", "in_place", "threads", "chunk", "lds_bytes")
+ONLINE_LANES_PER_NODE, ONLINE_THREAD_PER_NODE = 0, 1
+
+
+def train_online_route(c: int, xdim: int, ydim: int, dtype: int = _capi.PXSOM_F32, metric: int = 2) -> dict:
+    """The launch ``train_online`` would make for rows of ``c`` channels (``dtype``: a PXSOM_F* code) on an
+    ``xdim`` x ``ydim`` map under ``metric``, by the library's own planning function (include/pxsom.h
+    pxsom_train_online_route): family, width (CH | CMAX), span (L | MAXT), in_place, threads, chunk, lds_bytes.  Raises the
+    PxsomError the training call would raise for the shape.  Host arithmetic: no GPU needed."""
+    out = np.empty(len(ONLINE_ROUTE_FIELDS), dtype=np.int32)
+    rc = _capi.lib().pxsom_train_online_route(int(c), int(xdim), int(ydim), int(dtype), int(metric), out.ctypes.data)
+    _capi.check(rc, "pxsom_train_online_route")
+    return dict(zip(ONLINE_ROUTE_FIELDS, (int(v) for v in out)))
+
+
+def train_online_routes(shapes) -> np.ndarray:
+    """``train_online_route`` for a table of shapes at once: ``shapes`` [count, 5] int32 rows (c, xdim, ydim, dtype,
+    metric); returns [count, 1 + 7] int32 rows (status, then ONLINE_ROUTE_FIELDS -- all -1 where the status is not 0)."""
+    shapes = np.ascontiguousarray(shapes, dtype=np.int32)
+    if shapes.ndim != 2 or shapes.shape[1] != 5:
+        raise ValueError("shapes must be [count, 5]: c, xdim, ydim, dtype, metric")
+    out = np.empty((shapes.shape[0], 1 + len(ONLINE_ROUTE_FIELDS)), dtype=np.int32)
+    _capi.check(_capi.lib().pxsom_train_online_routes(shapes.shape[0], shapes.ctypes.data, out.ctypes.data),
+                "pxsom_train_online_routes")
+    return out
+
+
 def batch_train_steps(x: torch.Tensor, state: BatchTrainState, g_begin: int, g_end: int, total_steps: int,
                       alpha_range, radius_range, unfused: bool = False, comm: "RankComm" = None,
                       w0: Optional[torch.Tensor] = None) -> None:

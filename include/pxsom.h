@@ -454,6 +454,25 @@ int pxsom_train_online_metric(const void *x_dev, int64_t n, int c, int64_t ldx, 
                               int xdim, int ydim, int rlen, double a0, double a1, double r0, double r1,
                               const int64_t *order_dev, int metric, int flags, void *stream);
 
+/* ---- the launch an online training call would make (host arithmetic, no GPU call; works without a device) --------
+ * pxsom_train_online[_ex] (metric 2) and pxsom_train_online_metric (1, 3, 4) pick one of their kernel forms from
+ * k = xdim * ydim and c alone; this query runs the same planning function the launch runs and fills out[0 .. 6]:
+ *   [0] family     PXSOM_ONLINE_LANES_PER_NODE (Euclidean, small maps) or PXSOM_ONLINE_THREAD_PER_NODE
+ *   [1] CH, channels per lane            | CMAX, the register width of a node (0: the codebook is not in registers)
+ *   [2] L, lanes per node                | MAXT, the kernel's thread bound
+ *   [3] in_place   CMAX 0 only: the codebook does not fit the LDS beside the row ring and is trained where it lies
+ *   [4] threads of the one workgroup   [5] chunk: steps whose rows are gathered ahead together   [6] LDS bytes
+ * Returns PXSOM_OK, or the status and pxsom_last_error() message the training call gives for the shape (c or the grid
+ * past PXSOM_MAX_CHANNELS / PXSOM_MAX_NODES, a dtype or metric it does not know, no LDS for the row ring); the record is
+ * then all -1.  The dtype is validated and does not change the form.  A symbol added under ABI 9, none changed.
+ * pxsom_train_online_routes: the same for `count` shapes at once -- shapes [count][5] = (c, xdim, ydim, dtype, metric),
+ * out [count][1 + 7] = (status, record); host pointers.  Returns PXSOM_OK unless the table itself is bad. */
+#define PXSOM_ONLINE_LANES_PER_NODE 0
+#define PXSOM_ONLINE_THREAD_PER_NODE 1
+#define PXSOM_ONLINE_ROUTE_FIELDS 7
+int pxsom_train_online_route(int c, int xdim, int ydim, int dtype, int metric, int32_t *out);
+int pxsom_train_online_routes(int64_t count, const int32_t *shapes, int32_t *out);
+
 /* ---- cell cluster masks: border erosion + label lookup over a segmentation image (K10) ----------------------
  * reference: ark/utils/data_utils.py erode_mask (skimage.segmentation.find_boundaries, then np.where(edges == 0, seg, 0)),
  * relabel_segmentation / label_cells_by_cluster / map_segmentation_labels.  One stream-ordered pass over seg_dev [h, w]

@@ -592,32 +592,16 @@ def test_fuzz_metric_assign():
 
 
 def online_metric_route(k, c):
-    """The launch of pxsom_train_online_metric for k nodes x c channels, by the rule of train_online_metric_typed and
-    launch_online (csrc/pxsom_online.h): "register" (CMAX > 0: rows in registers, codebook in registers), "lds" (CMAX 0,
-    codebook in LDS beside the row ring), "in_place" (CMAX 0, the codebook does not fit: trained where it lies), or
-    "unsupported" (more than 1024 nodes or channels: PXSOM_ERR_UNSUPPORTED)."""
-    if k > 1024 or c > 1024:
+    """The launch of pxsom_train_online_metric for k nodes x c channels, as the library's own planning function gives it
+    (pxsom_train_online_route; host arithmetic, no GPU): "register" (CMAX > 0: rows in registers, codebook in registers),
+    "lds" (CMAX 0, codebook in LDS beside the row ring), "in_place" (CMAX 0, the codebook does not fit: trained where it
+    lies), or "unsupported" (more than 1024 nodes or channels: PXSOM_ERR_UNSUPPORTED)."""
+    from ark_analysis_amd import som_device
+    status, _, width, _, in_place = (int(v) for v in som_device.train_online_routes([[c, k, 1, 0, 1]])[0, :5])
+    if status == -2:
         return "unsupported"
-    if (k <= 256 and c <= 64) or (k <= 512 and c <= 40):
-        return "register"
-    bd = (k + 63) // 64 * 64
-    nwv = bd // 64
-
-    def plan(in_lds):
-        fixed = (c * k * 8 if in_lds else 0) + 2 * nwv * 8 + 2 * nwv * 4 + nwv * 8 + 2 * 64 * 8 + 64
-        chunk = 64
-        while chunk > 8 and fixed + 2 * chunk * c * 8 > 150 * 1024:
-            chunk >>= 1
-        while (chunk * c + bd - 1) // bd > 16:
-            chunk >>= 1
-        return chunk, fixed + 2 * chunk * c * 8
-
-    chunk, lds = plan(True)
-    if chunk < 1 or lds > 160 * 1024:
-        chunk, lds = plan(False)
-        assert chunk >= 1 and lds <= 160 * 1024
-        return "in_place"
-    return "lds"
+    assert status == 0, status
+    return "register" if width > 0 else "in_place" if in_place else "lds"
 
 
 ONLINE_METRIC_ROUTES = ("register", "lds", "in_place", "unsupported")
