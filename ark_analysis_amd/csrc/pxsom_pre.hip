@@ -183,7 +183,8 @@ __global__ __launch_bounds__(256) void blur_cols_lds_kernel(const double *__rest
 // pass A: keep flag per row and per-workgroup kept counts; pass B: exclusive scan of the counts (one
 // workgroup); pass C: rows rewritten as x / rowsum at their compacted position, in pixel order.
 // f32: the matrix holds float32 values (widened) and pandas works on a float32 frame: sum and division in
-// binary32.
+// binary32.  DataFrame.sum skips NaN (skipna: the NaNs are set to 0 before the sum), and NaN != 0 holds: a row with a
+// NaN is kept when the sum of its other values passes, and its NaN entries stay NaN after the division.
 __device__ __forceinline__ bool row_keep(const double *__restrict__ row, int c, double thresh, double &s, int f32)
 {
     bool any = false;
@@ -191,7 +192,7 @@ __device__ __forceinline__ bool row_keep(const double *__restrict__ row, int c, 
         float acc = 0.f;
         for (int j = 0; j < c; j++) {
             const float v = (float)row[j];
-            acc += v;
+            acc += v == v ? v : 0.f;
             any |= (v != 0.f);
         }
         s = (double)acc;
@@ -199,7 +200,7 @@ __device__ __forceinline__ bool row_keep(const double *__restrict__ row, int c, 
         double acc = 0.0;  // left-to-right, as pandas' DataFrame.sum(axis=1) adds the columns
         for (int j = 0; j < c; j++) {
             const double v = row[j];
-            acc += v;
+            acc += v == v ? v : 0.0;
             any |= (v != 0.0);
         }
         s = acc;

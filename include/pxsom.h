@@ -267,7 +267,8 @@ int pxsom_batch_train_finish(const double *wbuf_dev, const double *stats_ring_de
  * q = pxsom_exact_sum_quantum(max |x| over the job's rows, most rows any step holds over all ranks) makes every partial
  * sum exactly representable, hence every addition exact, hence the statistics -- and the whole run -- independent of
  * order, workgroup count and rank count.  The rounding is part of the rule: orc_som_batch_sched takes the same q.
- * pxsom_absmax: max |x| over the finite entries of a matrix into out_dev[0] (0 when there is none). */
+ * pxsom_absmax: max |x| over the finite entries of a matrix into out_dev[0] (0 when there is none: a matrix of
+ * NaN / +-inf only, or n = 0; a negative entry counts by its magnitude). */
 double pxsom_exact_sum_quantum(double value_bound, int64_t rows_bound);
 int pxsom_absmax(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, double *out_dev, void *stream);
 
@@ -361,6 +362,9 @@ int pxsom_gaussian_blur_hwc(double *img_dev, double *tmp_dev, int h, int w, int 
 /* reference: pixie_preprocessing.py:67-75 + pixel_cluster_utils.normalize_rows (:126-130):
  * keep pixel i iff rowsum_i > thresh and any(x_ij != 0); out row = x_i / rowsum_i (left-to-right
  * binary64 row sum, as pandas computes it).  Kept rows are compacted in pixel order.
+ * As in pandas, the row sum skips NaN (DataFrame.sum, skipna) and NaN != 0 holds: a row with a NaN is judged by the
+ * sum of its other values, and its NaN entries stay NaN.  The comparison with thresh is strict; a kept row whose
+ * sum is 0 or infinite comes out as the division gives it (inf, NaN, 0).
  *   out_rows_dev [<= n, c] binary64, out_index_dev [<= n] int64 flat pixel index of each kept row,
  *   out_count_dev [1] int64.  workspace from pxsom_rownorm_workspace_bytes(n). */
 size_t pxsom_rownorm_workspace_bytes(int64_t n);
@@ -379,7 +383,10 @@ int pxsom_normalize_columns(const double *x_dev, int64_t n, int c, int64_t ldx,
  * type-7 (linear) quantile of the kept values (keep_mode 0: != 0 and not NaN, 1: > 0, 2: not NaN) of each
  * column.
  * out_dev [c] binary64 (NaN for a column with no kept value).  Exact: MSB-first radix select on the
- * binary64 bit patterns, then numpy's interpolation formula.  Note pandas' effective q is (q*100)/100. */
+ * binary64 bit patterns, then numpy's interpolation formula.  Note pandas' effective q is (q*100)/100.
+ * Infinite values are kept and ordered like numbers; where numpy's interpolation then meets inf - inf the result is
+ * NaN, as numpy's is.  The select orders -0.0 below +0.0, numpy's sort leaves their order open: the SIGN of a zero
+ * result may differ from numpy's (keep_mode 2 only; the other modes drop zeros), its value does not. */
 size_t pxsom_quantile_workspace_bytes(int64_t n, int c);
 int pxsom_quantile_nonzero(const double *x_dev, int64_t n, int c, int64_t ldx, double q,
                            int keep_mode, double *out_dev, void *workspace_dev,
@@ -412,6 +419,8 @@ int pxsom_scaled_rowsum_f64(const double *img_dev, int64_t n, int c, int64_t ldx
  * LAST row, like the sequential numpy assignment.  status_dev [1] int32 comes back 0, or with
  * PXSOM_MASK_BAD_LABEL (a label outside the LUT or unmapped: the reference raises KeyError) and / or
  * PXSOM_MASK_BAD_PIXEL (a coordinate outside the image: IndexError) set; the mask is then unspecified.
+ * A NEGATIVE flat position row_index * W + column_index is PXSOM_MASK_BAD_PIXEL here, where numpy's fancy assignment
+ * would wrap it to the end of the image: the reference's tables never hold one, and the kernel does not imitate the wrap.
  * workspace: pxsom_cluster_mask_workspace_bytes(h, w) (one int64 per pixel: index of the winning row). */
 #define PXSOM_LUT_UNMAPPED (-2147483647 - 1)
 #define PXSOM_MASK_BAD_LABEL 1

@@ -287,7 +287,9 @@ def test_fuzz_online_training(oracle):
 
 def test_fuzz_preprocessing(oracle):
     """K2-K5 and the small label kernels on random shapes: blur (binary64 and float32 semantics), row-sum filter +
-    normalisation, column normalisation, non-zero / positive quantiles against numpy, pair histogram, relabel."""
+    normalisation, column normalisation, non-zero / positive quantiles against numpy, pair histogram, relabel.
+    (Small non-negative images in fresh aligned tensors; test_gpu_fuzz_preprocessing.py sweeps the same kernels by
+    route class, with hostile values and sentinel guards round every output.)"""
     from scipy import ndimage
     from ark_analysis_amd import som_device as sd
     rs = np.random.RandomState(SEED + 3)
