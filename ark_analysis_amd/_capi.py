@@ -114,6 +114,7 @@ SYMBOLS = {
                                _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     "pxsom_neighbor_counts": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _vp, _vp]),
     "pxsom_nearest_type_means": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f64, _vp, _vp]),
+    "pxsom_silhouette": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

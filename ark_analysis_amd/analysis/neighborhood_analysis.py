@@ -5,12 +5,14 @@ in one device launch over the centroid columns of the cell table (pxsom_neighbor
 reads one N x N distance matrix per FOV from ``dist_mat_dir``; here that directory is never opened.
 ``generate_cluster_matrix_results`` runs k-means over the counts on the host and builds the reference's three tables; its
 first frame carries the ``kmeans_neighborhood`` column that ``utils.data_utils.generate_and_save_neighborhood_cluster_masks``
-consumes.
+consumes.  Between the two, ``compute_cluster_metrics_inertia`` and ``compute_cluster_metrics_silhouette`` sweep k: the
+fits on the host, the silhouette scores of every k from one device call (pxsom_silhouette); they return a
+``pandas.Series`` indexed by ``cluster_num`` where the reference returns an ``xarray.DataArray``.
 
 The notebook's other two steps, the cell-distance and the diversity analysis, are in ``cell_neighborhood_stats``.
 
 Not mirrored: ``calc_dist_matrix`` and the ``.xr`` files (xarray is not a dependency here), the enrichment statistics,
-the mixing scores, the k-means inertia / silhouette sweeps and the plots."""
+the mixing scores and the plots."""
 import warnings
 
 import numpy as np
@@ -129,3 +131,32 @@ def generate_cluster_matrix_results(all_data, neighbor_mat, cluster_num, seed=42
     means = markers.groupby([cluster_label_col]).mean()
     means.index = ["Cluster" + str(c) for c in means.index]
     return clustered, per_type, means
+
+
+def _sweep_data(neighbor_mat, min_k, max_k, included_fovs, fov_col, label_col, cell_col):
+    """The checks and the column handling the two sweeps share: the rows of the included FOVs without the id columns."""
+    if included_fovs is None:
+        included_fovs = neighbor_mat[fov_col].unique()
+    if min_k < 2 or max_k < 2:
+        raise ValueError("Invalid k provided for clustering")
+    verify_in_list(fov_names=included_fovs, unique_fovs=neighbor_mat[fov_col].unique())
+    data = neighbor_mat[neighbor_mat[fov_col].isin(included_fovs)]
+    return data.drop([fov_col, label_col, cell_col], axis=1)
+
+
+def compute_cluster_metrics_inertia(neighbor_mat, min_k=2, max_k=10, seed=42, included_fovs=None, fov_col=_FOV_ID,
+                                    label_col=_CELL_LABEL, cell_col=_CELL_TYPE):
+    """The k-means inertia of the neighbourhood matrix for every k of ``min_k .. max_k`` (both at least 2), over the
+    rows of ``included_fovs`` (default: all).  Returns ``spatial_analysis_utils.compute_kmeans_inertia``'s Series."""
+    data = _sweep_data(neighbor_mat, min_k, max_k, included_fovs, fov_col, label_col, cell_col)
+    return spatial_analysis_utils.compute_kmeans_inertia(neighbor_mat_data=data, min_k=min_k, max_k=max_k, seed=seed)
+
+
+def compute_cluster_metrics_silhouette(neighbor_mat, min_k=2, max_k=10, seed=42, included_fovs=None, fov_col=_FOV_ID,
+                                       label_col=_CELL_LABEL, cell_col=_CELL_TYPE, subsample=None):
+    """The silhouette score of the k-means clusters of the neighbourhood matrix for every k of ``min_k .. max_k`` (both
+    at least 2), over the rows of ``included_fovs`` (default: all); ``subsample`` rows per cluster are scored when it is
+    given.  Returns ``spatial_analysis_utils.compute_kmeans_silhouette``'s Series."""
+    data = _sweep_data(neighbor_mat, min_k, max_k, included_fovs, fov_col, label_col, cell_col)
+    return spatial_analysis_utils.compute_kmeans_silhouette(neighbor_mat_data=data, min_k=min_k, max_k=max_k, seed=seed,
+                                                            subsample=subsample)

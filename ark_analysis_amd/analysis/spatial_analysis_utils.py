@@ -4,8 +4,14 @@
 one pxsom_neighbor_counts launch and the N x N matrix is never built.  Not mirrored: ``calc_dist_matrix``
 and its ``.xr`` files (xarray is not a dependency here), the distance-feature columns
 (``append_distance_features_to_dataset``; the cell-distance analysis is ``cell_neighborhood_stats``), the enrichment statistics
-(``compute_close_cell_num``, ``calculate_enrichment_stats``), the k-means inertia / silhouette sweeps and everything that
-plots."""
+(``compute_close_cell_num``, ``calculate_enrichment_stats``) and everything that plots.
+
+``compute_kmeans_inertia`` and ``compute_kmeans_silhouette`` are the reference's sweeps over k: the k-means fits stay on the
+host (as in ``generate_cluster_labels``), the silhouette scores of every k come from one pxsom_silhouette call (DESIGN.md
+K15) in place of one ``sklearn.metrics.silhouette_score`` per k.  They return a ``pandas.Series`` indexed by
+``cluster_num`` where the reference returns an ``xarray.DataArray``."""
+import warnings
+
 import numpy as np
 import pandas as pd
 
@@ -25,6 +31,18 @@ def _neighbor_counts_device(xy: np.ndarray, types: np.ndarray, seg: np.ndarray, 
         torch.from_numpy(np.ascontiguousarray(types, dtype=np.int32)).to(dev),
         torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int64)).to(dev), n_types, distlim, self_neighbor)
     return counts.cpu().numpy()
+
+
+def _silhouette_device(x: np.ndarray, labelings: np.ndarray, n_clusters) -> np.ndarray:
+    """som_device.silhouette_scores on host arrays: ``x`` [n, d] float64, ``labelings`` [M, n] with labeling m in
+    [0, n_clusters[m]) -> [M] float64 on the host."""
+    import torch
+    from .. import _capi, som_device
+    dev = _capi.require_gpu()
+    scores = som_device.silhouette_scores(
+        torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev),
+        torch.from_numpy(np.ascontiguousarray(labelings, dtype=np.int32)).to(dev), [int(k) for k in n_clusters])
+    return scores.cpu().numpy()
 
 
 def _freqs(counts: np.ndarray) -> np.ndarray:
@@ -72,3 +90,63 @@ def generate_cluster_labels(neighbor_mat_data, cluster_num, seed=42):
     from sklearn.cluster import KMeans
     fit = KMeans(n_clusters=cluster_num, random_state=seed, n_init=10).fit(neighbor_mat_data)
     return fit.labels_ + 1
+
+
+def _sweep_series(values, min_k, max_k):
+    return pd.Series(np.asarray(values, dtype=np.float64), index=pd.Index(np.arange(min_k, max_k + 1), name="cluster_num"))
+
+
+def _kmeans_sweep(neighbor_mat_data, min_k, max_k, seed):
+    """The reference's fit for every k of the sweep: ``KMeans(n_clusters=k, random_state=seed, n_init='auto')``."""
+    from sklearn.cluster import KMeans
+    return [KMeans(n_clusters=k, random_state=seed, n_init="auto").fit(neighbor_mat_data) for k in range(min_k, max_k + 1)]
+
+
+def compute_kmeans_inertia(neighbor_mat_data, min_k=2, max_k=10, seed=42):
+    """The k-means inertia of the rows of ``neighbor_mat_data`` for every k of ``min_k .. max_k`` (fits on the host).
+
+    Returns a float64 ``pandas.Series`` whose index, named ``cluster_num``, runs ``min_k .. max_k``."""
+    return _sweep_series([fit.inertia_ for fit in _kmeans_sweep(neighbor_mat_data, min_k, max_k, seed)], min_k, max_k)
+
+
+def _subsample_clusters(sub_dat, subsample, seed):
+    """The reference's per-cluster subsample of a frame with a ``cluster`` column: ``subsample`` rows of every cluster,
+    with replacement where the cluster is smaller."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=(DeprecationWarning, FutureWarning))   # apply over the grouping column
+        return sub_dat.groupby("cluster").apply(
+            lambda x: x.sample(subsample, replace=len(x) < subsample, random_state=seed)).reset_index(drop=True)
+
+
+def _encode_labels(labels, n_rows):
+    """Labels as 0 .. k' - 1 in sorted order (sklearn's LabelEncoder) and k'; sklearn's error unless 2 <= k' <= n - 1."""
+    uniques, codes = np.unique(np.asarray(labels), return_inverse=True)
+    if not 1 < len(uniques) < n_rows:
+        raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % len(uniques))
+    return codes.reshape(-1), len(uniques)
+
+
+def compute_kmeans_silhouette(neighbor_mat_data, min_k=2, max_k=10, seed=42, subsample=None):
+    """The silhouette score (Euclidean) of the k-means clusters of ``neighbor_mat_data`` for every k of
+    ``min_k .. max_k``.  The fits run on the host; the scores of the whole sweep come from one device call
+    (pxsom_silhouette), or from one call per k under ``subsample`` -- the number of rows drawn from every cluster
+    (with replacement from a smaller one) before scoring, as in the reference.
+
+    Returns a float64 ``pandas.Series`` whose index, named ``cluster_num``, runs ``min_k .. max_k``."""
+    values = np.asarray(neighbor_mat_data, dtype=np.float64)
+    if not np.isfinite(values).all():
+        raise ValueError("compute_kmeans_silhouette: neighbor_mat_data holds NaN or infinite values")
+    fits = _kmeans_sweep(neighbor_mat_data, min_k, max_k, seed)
+    if subsample is None:
+        encoded = [_encode_labels(fit.labels_, len(values)) for fit in fits]
+        scores = _silhouette_device(values, np.stack([codes for codes, _ in encoded]), [k for _, k in encoded])
+        return _sweep_series(scores, min_k, max_k)
+    scores = []
+    for fit in fits:
+        sub_dat = neighbor_mat_data.copy()
+        sub_dat["cluster"] = fit.labels_
+        sub_dat = _subsample_clusters(sub_dat, subsample, seed)
+        codes, k = _encode_labels(sub_dat["cluster"].to_numpy(), len(sub_dat))
+        rows = sub_dat.drop("cluster", axis=1).to_numpy(dtype=np.float64)
+        scores.append(_silhouette_device(rows, codes[None, :], [k])[0])
+    return _sweep_series(scores, min_k, max_k)

@@ -1071,3 +1071,73 @@ def nearest_type_means(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor,
     _capi.check(rc, "pxsom_nearest_type_means")
     means[order] = sorted_means
     return means
+
+
+# ---- silhouette sweeps (K15) ----------------------------------------------------------------------------------------
+SILHOUETTE_MAX_D = 64   # pxsom_silhouette keeps a row in registers
+SILHOUETTE_MAX_K = 32
+
+
+def _silhouette(x: torch.Tensor, labels: torch.Tensor, n_clusters):
+    """The checks, the sort by label and the one pxsom_silhouette call behind :func:`silhouette_samples` and
+    :func:`silhouette_scores`: ``(samples [M, n], scores [M], single)``, ``single`` when ``labels`` came as ``[n]``."""
+    if x.dim() != 2 or x.dtype != torch.float64:
+        raise ValueError("x must be an [n, d] float64 HBM tensor")
+    n, d = x.shape
+    if labels.dim() not in (1, 2) or labels.shape[-1] != n or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError("labels must be an [n] or [M, n] int32 / int64 HBM tensor on x's device")
+    single = labels.dim() == 1
+    n_labelings = 1 if single else labels.shape[0]
+    if n_labelings < 1:
+        raise ValueError("labels must hold at least one labeling")
+    ks = [operator.index(v) for v in (n_clusters if isinstance(n_clusters, (list, tuple, np.ndarray)) else [n_clusters])]
+    if len(ks) == 1:
+        ks = ks * n_labelings
+    if len(ks) != n_labelings:
+        raise ValueError("n_clusters must be one number or one per labeling: got %d for %d labelings"
+                         % (len(ks), n_labelings))
+    if not 1 <= d <= SILHOUETTE_MAX_D:
+        raise ValueError("d must lie in 1 .. %d (the device route keeps a row in registers), got %d"
+                         % (SILHOUETTE_MAX_D, d))
+    if min(ks) < 2 or max(ks) > SILHOUETTE_MAX_K:
+        raise ValueError("n_clusters must lie in 2 .. %d (the device route's limit), got %s" % (SILHOUETTE_MAX_K, ks))
+    if n < 2:
+        raise ValueError("the silhouette needs n >= 2 rows, got %d" % n)
+    if not x.is_cuda:
+        raise ValueError("x must be an [n, d] float64 HBM tensor")
+    dev = x.device
+    if labels.device != dev:
+        raise ValueError("labels must be an [n] or [M, n] int32 / int64 HBM tensor on x's device")
+    labels = labels.reshape(n_labelings, n)
+    limit = torch.tensor(ks, dtype=labels.dtype, device=dev).unsqueeze(1)
+    if not bool(((labels >= 0) & (labels < limit)).all().cpu()):
+        raise ValueError("labels must lie in [0, n_clusters)")
+    k = max(ks)
+    x = x.contiguous()
+    labels32 = labels.to(torch.int32).contiguous()
+    order = torch.argsort(labels32, dim=1, stable=True).to(torch.int32).contiguous()
+    counts = torch.empty((n_labelings, k), dtype=torch.int32, device=dev)
+    sums = torch.empty((n_labelings, n, k), dtype=torch.float64, device=dev)
+    samples = torch.empty((n_labelings, n), dtype=torch.float64, device=dev)
+    scores = torch.empty((n_labelings,), dtype=torch.float64, device=dev)
+    rc = _capi.lib().pxsom_silhouette(x.data_ptr(), n, d, labels32.data_ptr(), order.data_ptr(), n_labelings, k,
+                                      counts.data_ptr(), sums.data_ptr(), samples.data_ptr(), scores.data_ptr(),
+                                      _capi.stream_ptr())
+    _capi.check(rc, "pxsom_silhouette")
+    return samples, scores, single
+
+
+def silhouette_samples(x: torch.Tensor, labels: torch.Tensor, n_clusters) -> torch.Tensor:
+    """pxsom_silhouette: sklearn's ``silhouette_samples`` (Euclidean) of the rows of ``x`` ``[n, d]`` float64 under
+    ``labels`` -- ``[n]`` int32 / int64 with values in ``[0, n_clusters)``, giving ``[n]`` float64, or ``[M, n]`` for M
+    labelings in one call (``n_clusters`` then one number, or one per labeling), giving ``[M, n]``.  Distances in the
+    direct form in binary64 (equal rows are at exactly 0), every sum in an order fixed by the input: the same call
+    gives the same bits.  ``1 <= d <= 64``, ``2 <= n_clusters <= 32``, ``n >= 2``; a cluster may be empty."""
+    samples, _, single = _silhouette(x, labels, n_clusters)
+    return samples[0] if single else samples
+
+
+def silhouette_scores(x: torch.Tensor, labels: torch.Tensor, n_clusters) -> torch.Tensor:
+    """The mean of :func:`silhouette_samples` per labeling (sklearn's ``silhouette_score``), reduced on the device in a
+    fixed order: ``[M]`` float64 (``[1]`` for ``labels`` of shape ``[n]``)."""
+    return _silhouette(x, labels, n_clusters)[1]

@@ -621,6 +621,33 @@ int pxsom_neighbor_counts(const double *xy_dev, const int32_t *type_dev, const i
 int pxsom_nearest_type_means(const double *xy_dev, const int32_t *type_dev, const int64_t *seg_dev, int64_t n_fovs,
                              int64_t n, int n_types, int k, double s_zero, float *means_dev, void *stream);
 
+/* ---- silhouette coefficients of the rows of a matrix under several labelings at once (K15) ---------------------------
+ * reference: sklearn.metrics.silhouette_samples / silhouette_score (Euclidean), which
+ * ark/analysis/spatial_analysis_utils.py compute_kmeans_silhouette calls once per k.  Stream-ordered launches cover every
+ * labeling and the N x N matrix is never built.
+ *   x_dev        [n, d] binary64, row-major; 1 <= d <= 64 and 2 <= n < 2^31 (the device route's limits)
+ *   labels_dev   [n_labelings, n] int32, values in [0, k)
+ *   order_dev    [n_labelings, n] int32: for every labeling a permutation of 0 .. n - 1 that lists the rows of cluster 0,
+ *                then those of cluster 1, ... (a stable argsort of the labels)
+ *   k            2 .. 32 (the device route's limit); a labeling may leave clusters empty
+ *   counts_dev   [n_labelings, k] int32, written: the cluster sizes
+ *   sums_dev     [n_labelings, n, k] binary64, written:
+ *                  S[m, i, c] = sum over j with labels[m, j] == c of sqrt(sum_t (x[i, t] - x[j, t])^2)
+ *                every difference rounded once, every square added by one fused multiply-add in the order of t, the square
+ *                root correctly rounded, the distances of a cluster added one by one in the order `order` lists them:
+ *                no floating-point atomic anywhere, the same input gives the same bits.  Equal rows are at distance 0.
+ *   samples_dev  [n_labelings, n] binary64, written: with c_i = labels[m, i],
+ *                  a = S[i, c_i] / (n_{c_i} - 1), b = min over c != c_i with n_c > 0 of S[i, c] / n_c,
+ *                  s = (b - a) / max(a, b), and s = 0 when n_{c_i} == 1 or the quotient is NaN (silhouette_samples' rules)
+ *   scores_dev   [n_labelings] binary64, written: the mean of samples[m, :], reduced in a fixed order
+ * Every entry of the four outputs is written (the caller need not clear them).  A label outside [0, k) is counted nowhere
+ * and used as no index (its sample is NaN), run boundaries are clamped to [0, n] and an entry of order_dev outside [0, n)
+ * stands for a row of zeros: bad device-side input gives wrong rows, never an access outside the arrays.  d, k, n or
+ * n_labelings outside their limits, or a null pointer: PXSOM_ERR_INVALID_ARG before any HIP call. */
+int pxsom_silhouette(const double *x_dev, int64_t n, int d, const int32_t *labels_dev, const int32_t *order_dev,
+                     int n_labelings, int k, int32_t *counts_dev, double *sums_dev, double *samples_dev,
+                     double *scores_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
