@@ -115,6 +115,11 @@ SYMBOLS = {
     "pxsom_neighbor_counts": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _vp, _vp]),
     "pxsom_nearest_type_means": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f64, _vp, _vp]),
     "pxsom_silhouette": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pxsom_label_components_workspace_bytes": (_sz, [_i32, _i32]),
+    "pxsom_label_components": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "pxsom_components_select": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _i64, _vp]),
+    "pxsom_gaussian_blur_plane_mode": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "pxsom_binarize_plane": (_i32, [_vp, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

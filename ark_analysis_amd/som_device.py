@@ -713,12 +713,19 @@ def check_blur_sigma(sigma: float) -> None:
 
 
 def gaussian_blur_plane(plane: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None,
-                        tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """scipy.ndimage.gaussian_filter(plane, sigma) of a contiguous ``[H, W]`` HBM plane in its own dtype (uint8, int16,
-    uint16, int32 or float32): each pass stored in that dtype, as scipy stores it.  sigma <= 1e-15 skips both axes
-    (scipy's rule): the result is a copy.  ``out`` may be ``plane`` itself."""
+                        tmp: Optional[torch.Tensor] = None, mode: str = "reflect") -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(plane, sigma, mode=mode) of a contiguous ``[H, W]`` HBM plane in its own dtype (uint8,
+    int16, uint16, int32, float32 or float64): each pass stored in that dtype, as scipy stores it.  sigma <= 1e-15 skips
+    both axes (scipy's rule): the result is a copy.  ``out`` may be ``plane`` itself.  ``mode``: scipy's border, "reflect"
+    (the default) or "nearest".  The default mode on the five dtypes up to float32 is pxsom_gaussian_blur_plane, route and
+    bits as before the keyword existed; "nearest", and float64 planes (which this function used to refuse) under either
+    mode, go to pxsom_gaussian_blur_plane_mode."""
+    if mode not in BLUR_MODES:
+        raise ValueError("mode must be 'reflect' or 'nearest', got %r" % (mode,))
+    if mode != "reflect" or plane.dtype == torch.float64:
+        return gaussian_blur_plane_mode(plane, sigma, mode, out=out, tmp=tmp)
     if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in PLANE_DTYPES:
-        raise ValueError("plane must be a contiguous 2-D uint8 / int16 / uint16 / int32 / float32 HBM tensor")
+        raise ValueError("plane must be a contiguous 2-D uint8 / int16 / uint16 / int32 / float32 / float64 HBM tensor")
     h, w = plane.shape
     if h == 0 or w == 0:
         raise ValueError("plane must not be empty")
@@ -740,6 +747,188 @@ def gaussian_blur_plane(plane: torch.Tensor, sigma: float, out: Optional[torch.T
                                                PLANE_DTYPES[plane.dtype], weights.ctypes.data, radius, _capi.stream_ptr())
     _capi.check(rc, "pxsom_gaussian_blur_plane")
     return out
+
+
+BLUR_MODES = {"reflect": 0, "nearest": 1}          # include/pxsom.h PXSOM_BLUR_REFLECT / PXSOM_BLUR_NEAREST
+PLANE_MODE_DTYPES = {**PLANE_DTYPES, torch.float64: 6}
+
+
+def gaussian_blur_plane_mode(plane: torch.Tensor, sigma: float, mode: str, out: Optional[torch.Tensor] = None,
+                             tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(plane, sigma, mode=mode) through pxsom_gaussian_blur_plane_mode: the plane blur of
+    :func:`gaussian_blur_plane` with the border "reflect" or "nearest" and float64 planes beside the others."""
+    if mode not in BLUR_MODES:
+        raise ValueError("mode must be 'reflect' or 'nearest', got %r" % (mode,))
+    if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in PLANE_MODE_DTYPES:
+        raise ValueError("plane must be a contiguous 2-D uint8 / int16 / uint16 / int32 / float32 / float64 HBM tensor")
+    h, w = plane.shape
+    if h == 0 or w == 0:
+        raise ValueError("plane must not be empty")
+    check_blur_sigma(sigma)
+    if out is None:
+        out = torch.empty_like(plane)
+    elif out.shape != plane.shape or out.dtype != plane.dtype or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous HBM tensor of the plane's shape and dtype")
+    if float(sigma) <= 1e-15:
+        if out.data_ptr() != plane.data_ptr():
+            out.copy_(plane)
+        return out
+    if tmp is None:
+        tmp = torch.empty_like(plane)
+    elif tmp.shape != plane.shape or tmp.dtype != plane.dtype or not tmp.is_cuda or not tmp.is_contiguous():
+        raise ValueError("tmp must be a contiguous HBM tensor of the plane's shape and dtype")
+    weights, radius = gaussian_kernel1d(float(sigma))
+    rc = _capi.lib().pxsom_gaussian_blur_plane_mode(plane.data_ptr(), out.data_ptr(), tmp.data_ptr(), h, w,
+                                                    PLANE_MODE_DTYPES[plane.dtype], weights.ctypes.data, radius,
+                                                    BLUR_MODES[mode], _capi.stream_ptr())
+    _capi.check(rc, "pxsom_gaussian_blur_plane_mode")
+    return out
+
+
+# ---- object masks (K16): labelling, the area passes, the foreground predicates ----------------------------------------
+SELECT_FILL, SELECT_KEEP = 0, 1                      # include/pxsom.h PXSOM_SELECT_*
+BIN_POSITIVE, BIN_LEVEL, BIN_LOCAL = 0, 1, 2         # PXSOM_BIN_*
+CCL_TILE = 64                                        # kTile of csrc/pxsom_ccl.hip
+
+
+def _binary_plane(fg: torch.Tensor, what: str) -> torch.Tensor:
+    if fg.dim() != 2 or not fg.is_cuda or fg.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("%s must be a 2-D uint8 or bool HBM tensor" % what)
+    if fg.shape[0] == 0 or fg.shape[1] == 0:
+        raise ValueError("%s must not be empty" % what)
+    if fg.shape[1] > 1 and fg.stride(1) != 1:
+        raise ValueError("%s rows must be contiguous (stride(1) == 1)" % what)
+    return fg.view(torch.uint8) if fg.dtype == torch.bool else fg
+
+
+def _label_plane(t: Optional[torch.Tensor], h: int, w: int, device, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty((h, w), dtype=torch.int32, device=device)
+    if t.shape != (h, w) or t.dtype != torch.int32 or not t.is_cuda or (w > 1 and t.stride(1) != 1):
+        raise ValueError("%s must be a [H, W] int32 HBM tensor with contiguous rows" % what)
+    return t
+
+
+def _ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def label_components(fg: torch.Tensor, connectivity: int, invert: bool = False, out: Optional[torch.Tensor] = None,
+                     capacity: Optional[int] = None):
+    """``skimage.measure.label(fg != 0, connectivity=connectivity)`` of a ``[H, W]`` uint8 / bool HBM plane (rows
+    contiguous, any row stride); with ``invert`` the pixels equal to 0 are the foreground.  Returns ``(labels, n, areas)``,
+    all in HBM: ``labels`` int32 ``[H, W]`` (``out`` if given: rows contiguous, any row stride), background 0, components
+    numbered by their first pixel in raster order; ``n`` int32 ``[1]``, the count; ``areas`` int32 ``[capacity]`` with
+    ``areas[0]`` the background pixels (default capacity: every image's worst case, ``(H W + 1) // 2 + 1``)."""
+    fg = _binary_plane(fg, "fg")
+    h, w = fg.shape
+    if connectivity not in (1, 2):
+        raise ValueError("connectivity must be 1 or 2, got %r" % (connectivity,))
+    labels = _label_plane(out, h, w, fg.device, "out")
+    capacity = (h * w + 1) // 2 + 1 if capacity is None else int(capacity)
+    n = torch.empty(1, dtype=torch.int32, device=fg.device)
+    areas = torch.empty(capacity, dtype=torch.int32, device=fg.device)
+    lib = _capi.lib()
+    wsb = lib.pxsom_label_components_workspace_bytes(h, w)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=fg.device)
+    rc = lib.pxsom_label_components(fg.data_ptr(), h, w, _ld(fg), int(connectivity), int(bool(invert)), labels.data_ptr(),
+                                    _ld(labels), n.data_ptr(), areas.data_ptr(), capacity, ws.data_ptr(), wsb,
+                                    _capi.stream_ptr())
+    _capi.check(rc, "pxsom_label_components")
+    return labels, n, areas
+
+
+def components_select(labels: torch.Tensor, areas: torch.Tensor, mode: str, fg: Optional[torch.Tensor] = None,
+                      area_threshold: Optional[int] = None, min_area: int = 0, max_area: Optional[int] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pass over a label image and its area table (:func:`label_components`).
+    ``mode="fill"``: ``fg | (labels != 0 & areas[labels] < area_threshold)`` as uint8, ``labels`` being those of the
+    inverted ``fg`` under connectivity 1 -- ``morphology.remove_small_holes(fg, area_threshold)``.
+    ``mode="keep"``: ``labels`` where ``min_area <= areas[labels] <= max_area``, else 0 (int32; not renumbered);
+    ``out`` may be ``labels``."""
+    if mode not in ("fill", "keep"):
+        raise ValueError("mode must be 'fill' or 'keep', got %r" % (mode,))
+    if labels.dim() != 2 or labels.shape[0] == 0 or labels.shape[1] == 0:
+        raise ValueError("labels must be a non-empty [H, W] tensor")
+    h, w = labels.shape
+    labels = _label_plane(labels, h, w, labels.device, "labels")
+    if areas.dtype != torch.int32 or not areas.is_cuda or areas.dim() != 1 or not areas.is_contiguous() or not areas.numel():
+        raise ValueError("areas must be a contiguous int32 HBM vector")
+    lim = 2 ** 62
+    if mode == "fill":
+        if fg is None or area_threshold is None:
+            raise ValueError("mode 'fill' needs fg and area_threshold")
+        fg = _binary_plane(fg, "fg")
+        if fg.shape != (h, w):
+            raise ValueError("fg and labels must have one shape")
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.uint8, device=labels.device)
+        elif out.shape != (h, w) or out.dtype != torch.uint8 or not out.is_cuda or (w > 1 and out.stride(1) != 1):
+            raise ValueError("out must be a [H, W] uint8 HBM tensor with contiguous rows")
+        args = (SELECT_FILL, fg.data_ptr(), _ld(fg), 0, max(-lim, min(lim, int(area_threshold))))
+    else:
+        out = _label_plane(out, h, w, labels.device, "out")
+        hi = lim if max_area is None else max(-lim, min(lim, int(np.floor(max_area))))
+        args = (SELECT_KEEP, None, 0, max(-lim, min(lim, int(np.ceil(min_area)))), hi)
+    rc = _capi.lib().pxsom_components_select(args[0], args[1], args[2], labels.data_ptr(), _ld(labels), areas.data_ptr(),
+                                             areas.numel(), h, w, args[3], args[4], out.data_ptr(), _ld(out),
+                                             _capi.stream_ptr())
+    _capi.check(rc, "pxsom_components_select")
+    return out
+
+
+def binarize_plane(plane: torch.Tensor, mode: int = BIN_POSITIVE, level: float = 0.0,
+                   local: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The uint8 foreground of a contiguous float32 / float64 ``[H, W]`` HBM plane: ``v > 0`` (BIN_POSITIVE),
+    ``!(v < level) & v > 0`` (BIN_LEVEL) or ``v > local`` (BIN_LOCAL, ``local`` a plane of the same dtype and shape)."""
+    if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in (torch.float32, torch.float64):
+        raise ValueError("plane must be a contiguous 2-D float32 / float64 HBM tensor")
+    if plane.numel() == 0:
+        raise ValueError("plane must not be empty")
+    if mode == BIN_LOCAL and (local is None or local.shape != plane.shape or local.dtype != plane.dtype
+                              or not local.is_cuda or not local.is_contiguous()):
+        raise ValueError("local must be a contiguous HBM plane of the plane's shape and dtype")
+    h, w = plane.shape
+    out = torch.empty((h, w), dtype=torch.uint8, device=plane.device)
+    rc = _capi.lib().pxsom_binarize_plane(plane.data_ptr(), PLANE_MODE_DTYPES[plane.dtype], h, w, int(mode), float(level),
+                                          local.data_ptr() if mode == BIN_LOCAL else None, out.data_ptr(), w,
+                                          _capi.stream_ptr())
+    _capi.check(rc, "pxsom_binarize_plane")
+    return out
+
+
+def object_mask(img: torch.Tensor, sigma, thresh, hole_size, min_area, max_area, local_block=None) -> torch.Tensor:
+    """The device chain of ``_create_object_mask`` on a ``[H, W]`` HBM image -> int32 ``[H, W]`` labels in HBM.
+    float32 / float64 images go as they are, any other dtype is cast to float64 (skimage's ``preserve_range`` rule).
+      blur       ``sigma`` None: none; else ``gaussian_filter(x, sigma, mode='nearest')`` in x's dtype
+      threshold  ``thresh`` None: ``blur > 0``; an int: ``p = np.percentile(blur[blur != 0], thresh)``, foreground
+                 ``!(blur < p) & blur > 0``; "auto": ``blur > gaussian_filter(blur, (local_block - 1) / 6, mode='reflect')``
+      holes      ``hole_size`` None: none; else background components (4-neighbourhood) of area < hole_size are filled
+      labels     8-neighbourhood components, kept where ``min_area <= area <= max_area`` (not renumbered)
+    The percentile is the one value read back to the host: pxsom_quantile_f32 / pxsom_quantile_nonzero with their
+    ``!= 0`` keep rule (bits equal numpy's for both dtypes; a NaN pixel is dropped there where numpy's result turns NaN)."""
+    if img.dim() != 2 or not img.is_cuda or img.shape[0] == 0 or img.shape[1] == 0:
+        raise ValueError("img must be a non-empty 2-D HBM tensor")
+    x = img if img.dtype in (torch.float32, torch.float64) else img.to(torch.float64)
+    x = x.contiguous()
+    blur = x if sigma is None else gaussian_blur_plane(x, sigma, mode="nearest")
+    if thresh is None:
+        fg = binarize_plane(blur, BIN_POSITIVE)
+    elif isinstance(thresh, str):
+        if thresh != "auto" or local_block is None:
+            raise ValueError("thresh 'auto' needs local_block; got thresh=%r local_block=%r" % (thresh, local_block))
+        local = gaussian_blur_plane(blur, (float(local_block) - 1) / 6.0, mode="reflect")
+        fg = binarize_plane(blur, BIN_LOCAL, local=local)
+    else:
+        column = blur.reshape(-1, 1)
+        q = np.true_divide(thresh, 100)        # np.percentile's own division
+        p = (quantile_f32 if blur.dtype == torch.float32 else quantile_nonzero)(column, float(q), keep_mode=0)
+        fg = binarize_plane(blur, BIN_LEVEL, level=float(p.item()))
+    if hole_size is not None:
+        holes, _, hole_areas = label_components(fg, 1, invert=True)
+        fg = components_select(holes, hole_areas, "fill", fg=fg, area_threshold=hole_size)
+    labels, _, areas = label_components(fg, 2)
+    return components_select(labels, areas, "keep", min_area=min_area, max_area=max_area, out=labels)
 
 
 def zero_by_segmentation(img: torch.Tensor, seg: torch.Tensor, exclude: bool = True) -> torch.Tensor:

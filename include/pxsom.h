@@ -648,6 +648,63 @@ int pxsom_silhouette(const double *x_dev, int64_t n, int d, const int32_t *label
                      int n_labelings, int k, int32_t *counts_dev, double *sums_dev, double *samples_dev,
                      double *scores_dev, void *stream);
 
+/* ---- object masks: connected-component labelling and the passes around it (K16) --------------------------------------
+ * reference: ark/segmentation/ez_seg/ez_object_segmentation.py _create_object_mask (filters.gaussian, a threshold,
+ * morphology.remove_small_holes, measure.label(connectivity=2), regionprops_table area, map_array), which
+ * create_object_masks and ark/utils/masking_utils.py wrap.  Symbols added under ABI 9, none changed.
+ *
+ * pxsom_label_components: skimage.measure.label / scipy.ndimage.label of a binary plane.
+ *   fg_dev      [h, w] uint8, row stride ld >= w; a pixel is foreground when != 0 (invert = 0) or == 0 (invert = 1)
+ *   connectivity 1 (4-neighbourhood) or 2 (8-neighbourhood)
+ *   labels_dev  [h, w] int32, row stride ldo >= w, every pixel written: 0 for background; the component whose first
+ *               pixel in raster order comes earliest is 1, the next 2, ...
+ *   n_dev       [1] int32: the number of components
+ *   areas_dev   [capacity] int32, every entry written: areas[0] the background pixels, areas[l] the pixels of label
+ *               l < capacity, 0 past n.  A label >= capacity is counted nowhere: capacity = (h * w + 1) / 2 + 1 holds
+ *               every image (a 4-connected checkerboard has the most components).
+ * Integer arithmetic only (union-find with atomicMin on the parent index, int32 atomic adds for the areas): the same
+ * input gives the same bits on every run.  Workspace: pxsom_label_components_workspace_bytes(h, w) (one int32 per pixel
+ * and one count per 256 pixels; 0 for sizes the entry does not take).  Bad sizes, strides, connectivity, flag, capacity,
+ * pointers or workspace: PXSOM_ERR_INVALID_ARG before any HIP call; h * w beyond int32: PXSOM_ERR_UNSUPPORTED.
+ *
+ * pxsom_components_select: one pass that rewrites a label image from its area table (labels_dev [h, w] int32, row
+ * stride ldl; areas_dev [capacity]; a label >= capacity counts as area 0 and is never an index).
+ *   PXSOM_SELECT_FILL  out_dev uint8 [h, w]: out = (fg != 0) | (label != 0 && area[label] < area_hi), labels being those of
+ *                      the INVERTED plane under connectivity 1: morphology.remove_small_holes(fg, area_hi), strict <, no
+ *                      special case for a hole that touches the border.  fg_dev [h, w] uint8, row stride ldf; area_lo unused.
+ *   PXSOM_SELECT_KEEP  out_dev int32 [h, w]: out = label when area_lo <= area[label] <= area_hi, else 0; labels are not
+ *                      renumbered (map_array(labels, all, all * keep)).  fg_dev unused; out_dev may be labels_dev.
+ *
+ * pxsom_gaussian_blur_plane_mode: pxsom_gaussian_blur_plane with scipy's border mode as an argument -- PXSOM_BLUR_REFLECT
+ * (the K11 entry's, same bits) or PXSOM_BLUR_NEAREST (the index clamped to the line: skimage.filters.gaussian's default) --
+ * and PXSOM_SEG_F64 planes beside U8, I16, U16, I32 and F32.  Same arithmetic order (correlate1d's symmetric branch in
+ * binary64, no FMA contraction, each pass stored in the plane's dtype), same radius <= 64 limit (PXSOM_ERR_UNSUPPORTED).
+ *
+ * pxsom_binarize_plane: the uint8 foreground (1 / 0) of a contiguous [h, w] PXSOM_SEG_F32 or _F64 plane, out_dev row
+ * stride ldo; compared in binary64 (float32 widens exactly):
+ *   PXSOM_BIN_POSITIVE  v > 0
+ *   PXSOM_BIN_LEVEL     !(v < level) && v > 0          (np.where(v < p, 0, v) > 0)
+ *   PXSOM_BIN_LOCAL     v > local_dev[i]               (local_dev: a contiguous plane of the same dtype)
+ * Bad arguments: PXSOM_ERR_INVALID_ARG before any HIP call, for all four entries. */
+#define PXSOM_SELECT_FILL 0
+#define PXSOM_SELECT_KEEP 1
+#define PXSOM_BLUR_REFLECT 0
+#define PXSOM_BLUR_NEAREST 1
+#define PXSOM_BIN_POSITIVE 0
+#define PXSOM_BIN_LEVEL 1
+#define PXSOM_BIN_LOCAL 2
+size_t pxsom_label_components_workspace_bytes(int h, int w);
+int pxsom_label_components(const uint8_t *fg_dev, int h, int w, int64_t ld, int connectivity, int invert,
+                           int32_t *labels_dev, int64_t ldo, int32_t *n_dev, int32_t *areas_dev, int64_t capacity,
+                           void *workspace_dev, size_t workspace_bytes, void *stream);
+int pxsom_components_select(int mode, const uint8_t *fg_dev, int64_t ldf, const int32_t *labels_dev, int64_t ldl,
+                            const int32_t *areas_dev, int64_t capacity, int h, int w, int64_t area_lo, int64_t area_hi,
+                            void *out_dev, int64_t ldo, void *stream);
+int pxsom_gaussian_blur_plane_mode(const void *in_dev, void *out_dev, void *tmp_dev, int h, int w, int dtype,
+                                   const double *weights_host, int radius, int border, void *stream);
+int pxsom_binarize_plane(const void *plane_dev, int dtype, int h, int w, int mode, double level, const void *local_dev,
+                         uint8_t *out_dev, int64_t ldo, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
