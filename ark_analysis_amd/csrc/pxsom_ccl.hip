@@ -3,8 +3,8 @@
 //   pxsom_label_components          skimage.measure.label / scipy.ndimage.label of a binary plane (4- or 8-neighbourhood),
 //                                   with the component count and the area table
 //   pxsom_components_select         remove_small_holes' fill / the area filter of _create_object_mask, from the area table
-//   pxsom_gaussian_blur_plane_mode  pxsom_gaussian_blur_plane with a border argument (reflect / nearest) and a binary64 plane
 //   pxsom_binarize_plane            the three foreground predicates of _create_object_mask
+// (The blur of _create_object_mask is pxsom_gaussian_blur_plane_mode of pxsom_pre.hip.)
 //
 // Labelling is union-find on linear pixel indices, parent <= child everywhere, so the root of a component IS its first pixel
 // in raster order -- ranking the roots by index gives skimage's numbering.  Four stages:
@@ -17,15 +17,13 @@
 //   4. finish_labels_kernel  every other pixel copies its root's label; areas by int32 atomic adds: one per workgroup for
 //                            the label its 4096 pixels start with, one per run of equal labels in a wave for the others
 // Integer arithmetic only: whatever the order of the atomics, the final partition, the roots and so the labels are the same.
-#include <algorithm>
-
 #include "pxsom_common.h"
+#include "pxsom_plane.h"
 
 namespace {
 
 constexpr int kTile = 64;          // tile edge == wave width: lane <-> tile column
 constexpr int kChunk = 256;        // pixels per workgroup of the flat passes
-constexpr int kMaxRadius = 64;
 
 __device__ __forceinline__ int ld_relaxed(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -58,20 +56,12 @@ __device__ __forceinline__ void uf_union(int *parent, int a, int b)
     }
 }
 
-// workgroup b runs on XCD b % 8; neighbouring tiles go to one XCD (as the blur tiles of pxsom_pre.hip)
-__device__ __forceinline__ int64_t xcd_contiguous(int64_t b, int64_t nb)
-{
-    constexpr int kXcds = 8;
-    const int64_t per = (nb + kXcds - 1) / kXcds;
-    return (b % kXcds) * per + b / kXcds;     // may be >= nb: the caller skips those
-}
-
 __global__ __launch_bounds__(256) void tile_label_kernel(const uint8_t *__restrict__ src, int64_t ld, int h, int w, int invert,
                                                          int conn8, int *__restrict__ parent, int tiles_x, int64_t ntiles)
 {
     __shared__ int lab[kTile * kTile];
     __shared__ unsigned long long rowmask[kTile];
-    const int64_t tile = xcd_contiguous(blockIdx.x, ntiles);
+    const int64_t tile = xcd_contiguous(blockIdx.x, ntiles);   // neighbouring tiles go to one XCD
     if (tile >= ntiles) return;
     const int ty0 = (int)(tile / tiles_x) * kTile, tx0 = (int)(tile % tiles_x) * kTile;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -306,58 +296,7 @@ __global__ __launch_bounds__(256) void select_keep_kernel(const int32_t *__restr
     }
 }
 
-// ---- blur with a border policy ---------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
-
-struct Taps {
-    double w[kMaxRadius + 1];  // w[0] centre, w[d] weight at distance d (symmetric kernel)
-    int radius;
-};
-
-// scipy NI_EXTEND_REFLECT (d c b a | a b c d | d c b a), any i; NI_EXTEND_NEAREST (a a a | a b c d | d d d)
-__device__ __forceinline__ int border_idx(int i, int len, int nearest)
-{
-    if (nearest) return i < 0 ? 0 : (i >= len ? len - 1 : i);
-    if (len == 1) return 0;
-    const int sz2 = 2 * len;
-    int m = i % sz2;
-    if (m < 0) m += sz2;
-    return m < len ? m : sz2 - 1 - m;
-}
-
-// One pass of scipy's correlate1d, symmetric-kernel branch, as blur_pass_kernel of pxsom_pre.hip forms it:
-//   tmp = in[0]*w[0];  for d = r .. 1:  tmp += (in[-d] + in[+d]) * w[d]     in binary64, stored as T (a C cast)
-template <int AXIS, typename T>
-__global__ __launch_bounds__(256) void blur_mode_pass_kernel(const T *__restrict__ in, T *__restrict__ out, int H, int W,
-                                                             Taps taps, int nearest)
-{
-    const int64_t total = (int64_t)H * W;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int y = (int)(e / W);
-        const int xcol = (int)(e - (int64_t)y * W);
-        const int pos = AXIS == 0 ? y : xcol, len = AXIS == 0 ? H : W;
-        const int64_t stride = AXIS == 0 ? W : 1;
-        const int64_t base = e - (int64_t)pos * stride;
-        double tmp = (double)in[e] * taps.w[0];
-        const bool interior = pos >= taps.radius && pos + taps.radius < len;
-        for (int d = taps.radius; d >= 1; d--) {
-            const int lo = interior ? pos - d : border_idx(pos - d, len, nearest);
-            const int hi = interior ? pos + d : border_idx(pos + d, len, nearest);
-            tmp += ((double)in[base + (int64_t)lo * stride] + (double)in[base + (int64_t)hi * stride]) * taps.w[d];
-        }
-        out[e] = (T)tmp;
-    }
-}
-
-template <typename T>
-void launch_blur_mode(const void *in, void *out, void *tmp, int h, int w, const Taps &taps, int nearest, int grid,
-                      hipStream_t st)
-{
-    hipLaunchKernelGGL((blur_mode_pass_kernel<0, T>), dim3(grid), dim3(256), 0, st, static_cast<const T *>(in),
-                       static_cast<T *>(tmp), h, w, taps, nearest);
-    hipLaunchKernelGGL((blur_mode_pass_kernel<1, T>), dim3(grid), dim3(256), 0, st, static_cast<const T *>(tmp),
-                       static_cast<T *>(out), h, w, taps, nearest);
-}
 
 // the comparisons widen float32 exactly: what numpy compares in binary32 compares the same in binary64
 template <typename T>
@@ -376,11 +315,6 @@ __global__ __launch_bounds__(256) void binarize_kernel(const T *__restrict__ pla
 }
 
 #pragma clang fp contract(fast)
-
-inline int flat_grid(int64_t total)
-{
-    return (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, (int64_t)pxsom::device_cu_count() * 16));
-}
 
 inline int64_t ccl_chunks(int64_t total) { return (total + kChunk - 1) / kChunk; }
 
@@ -446,7 +380,7 @@ PXSOM_EXPORT int pxsom_components_select(int mode, const uint8_t *fg_dev, int64_
     if (!labels_dev || !areas_dev || !out_dev || (mode == PXSOM_SELECT_FILL && !fg_dev))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_components_select: null pointer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int grid = flat_grid((int64_t)h * w);
+    const int grid = pxsom::flat_grid((int64_t)h * w);
     if (mode == PXSOM_SELECT_FILL)
         hipLaunchKernelGGL(select_fill_kernel, dim3(grid), dim3(256), 0, st, fg_dev, ldf, labels_dev, ldl, areas_dev, capacity, h, w,
                            area_hi, static_cast<uint8_t *>(out_dev), ldo);
@@ -454,37 +388,6 @@ PXSOM_EXPORT int pxsom_components_select(int mode, const uint8_t *fg_dev, int64_
         hipLaunchKernelGGL(select_keep_kernel, dim3(grid), dim3(256), 0, st, labels_dev, ldl, areas_dev, capacity, h, w, area_lo,
                            area_hi, static_cast<int32_t *>(out_dev), ldo);
     PXSOM_LAUNCH_CHECK("pxsom_components_select kernel");
-    return PXSOM_OK;
-}
-
-PXSOM_EXPORT int pxsom_gaussian_blur_plane_mode(const void *in_dev, void *out_dev, void *tmp_dev, int h, int w, int dtype,
-                                                const double *weights_host, int radius, int border, void *stream)
-{
-    if (!in_dev || !out_dev || !tmp_dev || !weights_host || h < 1 || w < 1 || tmp_dev == in_dev || tmp_dev == out_dev)
-        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_gaussian_blur_plane_mode: bad arguments");
-    if (dtype != PXSOM_SEG_U8 && dtype != PXSOM_SEG_I16 && dtype != PXSOM_SEG_U16 && dtype != PXSOM_SEG_I32 &&
-        dtype != PXSOM_SEG_F32 && dtype != PXSOM_SEG_F64)
-        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_gaussian_blur_plane_mode: dtype %d is not u8 / i16 / u16 / i32 / f32 / f64", dtype);
-    if (border != PXSOM_BLUR_REFLECT && border != PXSOM_BLUR_NEAREST)
-        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_gaussian_blur_plane_mode: border %d", border);
-    if (radius < 0 || radius > kMaxRadius)
-        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_gaussian_blur_plane_mode: radius %d outside [0, %d]", radius, kMaxRadius);
-    Taps taps;
-    taps.radius = radius;
-    for (int d = 0; d <= radius; d++) taps.w[d] = weights_host[radius + d];
-    for (int d = radius + 1; d <= kMaxRadius; d++) taps.w[d] = 0.0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int grid = flat_grid((int64_t)h * w);
-    const int nearest = border == PXSOM_BLUR_NEAREST;
-    switch (dtype) {
-    case PXSOM_SEG_U8: launch_blur_mode<uint8_t>(in_dev, out_dev, tmp_dev, h, w, taps, nearest, grid, st); break;
-    case PXSOM_SEG_I16: launch_blur_mode<int16_t>(in_dev, out_dev, tmp_dev, h, w, taps, nearest, grid, st); break;
-    case PXSOM_SEG_U16: launch_blur_mode<uint16_t>(in_dev, out_dev, tmp_dev, h, w, taps, nearest, grid, st); break;
-    case PXSOM_SEG_I32: launch_blur_mode<int32_t>(in_dev, out_dev, tmp_dev, h, w, taps, nearest, grid, st); break;
-    case PXSOM_SEG_F32: launch_blur_mode<float>(in_dev, out_dev, tmp_dev, h, w, taps, nearest, grid, st); break;
-    default: launch_blur_mode<double>(in_dev, out_dev, tmp_dev, h, w, taps, nearest, grid, st); break;
-    }
-    PXSOM_LAUNCH_CHECK("blur_mode_pass_kernel");
     return PXSOM_OK;
 }
 
@@ -497,7 +400,7 @@ PXSOM_EXPORT int pxsom_binarize_plane(const void *plane_dev, int dtype, int h, i
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_binarize_plane: bad mode %d or no local plane", mode);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)h * w;
-    const int grid = flat_grid(total);
+    const int grid = pxsom::flat_grid(total);
     if (dtype == PXSOM_SEG_F32)
         hipLaunchKernelGGL(binarize_kernel<float>, dim3(grid), dim3(256), 0, st, static_cast<const float *>(plane_dev),
                            static_cast<const float *>(local_dev), total, w, mode, level, out_dev, ldo);

@@ -30,50 +30,23 @@
 #include <type_traits>
 
 #include "pxsom_common.h"
+#include "pxsom_keytable.h"
 
 namespace {
 
 constexpr int kWaves = 4;                      // waves per block, both kernels
-constexpr int64_t kDenseMaxEntries = int64_t(1) << 24;
 constexpr int kNucMaxCapacity = 128;
 constexpr int kBatch = 8;                      // member pixels whose loads are in flight together
 constexpr int kAcc = 2;                        // channel accumulators per lane: 128 channels per walk
 constexpr int64_t kNumpyBuffer = 8192;         // numpy's default ufunc buffer size (np.getbufsize())
 constexpr int kPairwiseBlock = 128;            // numpy's PW_BLOCKSIZE
 
-struct KeyTable {
-    const int32_t *keys;
-    const int32_t *lut;        // dense route: index of key_min + i in keys, -1 when absent; nullptr: binary search
-    int64_t n_keys;
-    int32_t key_min;
-    int64_t lut_size;
-};
-
+// dense cell index of a label: 0 is the background, -1
 template <typename TI>
 __device__ __forceinline__ int32_t dense_index(const KeyTable &t, TI label)
 {
     if (label == (TI)0) return -1;
-    const int32_t key = (int32_t)(int64_t)label;
-    if (t.lut) {
-        const int64_t d = (int64_t)key - t.key_min;
-        return d >= 0 && d < t.lut_size ? t.lut[d] : -1;
-    }
-    int64_t lo = 0, hi = t.n_keys;                    // first key >= `key`
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (t.keys[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < t.n_keys && t.keys[lo] == key ? (int32_t)lo : -1;
-}
-
-__global__ __launch_bounds__(256) void lut_scatter_kernel(const int32_t *__restrict__ keys, int64_t n, int32_t key_min,
-                                                          int64_t lut_size, int32_t *__restrict__ lut)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t d = (int64_t)keys[i] - key_min;
-        if (d >= 0 && d < lut_size) lut[d] = (int32_t)i;
-    }
+    return (int32_t)find_key(t, (int32_t)(int64_t)label);
 }
 
 __global__ __launch_bounds__(256) void init_kernel(int64_t n, unsigned long long *__restrict__ count,
@@ -431,39 +404,12 @@ __global__ __launch_bounds__(256) void walk_kernel(const T *__restrict__ img, Wa
     if (lane == 0) a.nuc_out[k] = best_k;
 }
 
-int label_bytes(int dt)
-{
-    switch (dt) {
-    case PXSOM_SEG_U8: return 1;
-    case PXSOM_SEG_I16: case PXSOM_SEG_U16: return 2;
-    case PXSOM_SEG_I32: case PXSOM_SEG_U32: return 4;
-    case PXSOM_SEG_I64: return 8;
-    default: return 0;
-    }
-}
-
-int image_bytes(int dt)
-{
-    switch (dt) {
-    case PXSOM_SEG_U8: return 1;
-    case PXSOM_SEG_I16: case PXSOM_SEG_U16: return 2;
-    case PXSOM_SEG_I32: case PXSOM_SEG_F32: return 4;
-    case PXSOM_SEG_F64: return 8;
-    default: return 0;
-    }
-}
-
 bool is_float(int dt) { return dt == PXSOM_SEG_F32 || dt == PXSOM_SEG_F64; }
 
 size_t lut_bytes(int64_t n_keys, int32_t key_min, int32_t key_max, int flags)
 {
-    if (n_keys <= 0 || key_max < key_min || (flags & PXSOM_CELLQUANT_FORCE_SEARCH)) return 0;
-    const int64_t range = (int64_t)key_max - key_min + 1;
-    if (range > kDenseMaxEntries || range > 16 * n_keys + 65536) return 0;   // the K10 rule
-    return (size_t)range * sizeof(int32_t);
+    return (flags & PXSOM_CELLQUANT_FORCE_SEARCH) ? 0 : pxsom::dense_lut_bytes(n_keys, key_min, key_max);
 }
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct Layout {
     size_t idx, nuc_idx, lut, nuc_lut, off, list, total;
@@ -477,33 +423,23 @@ Layout layout(int h, int w, int c, int img_dtype, int mode, int64_t n_keys, int3
     const size_t px = (size_t)h * (size_t)w;
     size_t at = 0;
     L.idx = at;
-    at += align256(px * sizeof(int32_t));
+    at += pxsom::align_up(px * sizeof(int32_t), 256);
     L.nuc_idx = at;
-    if (n_nuc_keys >= 0) at += align256(px * sizeof(int32_t));
+    if (n_nuc_keys >= 0) at += pxsom::align_up(px * sizeof(int32_t), 256);
     L.lut_b = lut_bytes(n_keys, key_min, key_max, flags);
     L.lut = at;
-    at += align256(L.lut_b);
+    at += pxsom::align_up(L.lut_b, 256);
     L.nuc_lut_b = n_nuc_keys > 0 ? lut_bytes(n_nuc_keys, nuc_key_min, nuc_key_max, flags) : 0;
     L.nuc_lut = at;
-    at += align256(L.nuc_lut_b);
+    at += pxsom::align_up(L.nuc_lut_b, 256);
     L.off = L.list = at;
     if (mode == PXSOM_CELLQUANT_TOTAL && c == 1 && is_float(img_dtype)) {
-        at += align256((size_t)(n_keys + 1) * sizeof(int64_t));
+        at += pxsom::align_up((size_t)(n_keys + 1) * sizeof(int64_t), 256);
         L.list = at;
-        at += align256(px * (size_t)image_bytes(img_dtype));
+        at += pxsom::align_up(px * (size_t)pxsom::plane_dtype_bytes(img_dtype), 256);
     }
     L.total = at;
     return L;
-}
-
-int build_lut(const int32_t *keys, int64_t n_keys, int32_t key_min, size_t bytes, int32_t *lut, hipStream_t st)
-{
-    PXSOM_HIP_TRY(hipMemsetAsync(lut, 0xFF, bytes, st));   // every slot -1: absent
-    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n_keys + 255) / 256, (int64_t)pxsom::device_cu_count() * 4));
-    hipLaunchKernelGGL(lut_scatter_kernel, dim3((unsigned)grid), dim3(256), 0, st, keys, n_keys, key_min,
-                       (int64_t)(bytes / sizeof(int32_t)), lut);
-    PXSOM_LAUNCH_CHECK("lut_scatter_kernel");
-    return PXSOM_OK;
 }
 
 template <bool kStats>
@@ -513,18 +449,11 @@ int launch_map(const void *seg, int seg_dtype, int h, int w, int64_t ld, const K
     const int segs = (w + 63) / 64;
     const int64_t blocks = ((int64_t)h * segs + kWaves - 1) / kWaves;
     if (blocks > 0x7fffffff) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_cellquant: image too large");
-#define PXSOM_CQ_MAP(TI)                                                                                            \
-    hipLaunchKernelGGL((map_kernel<TI, kStats>), dim3((unsigned)blocks), dim3(256), 0, st,                         \
-                       reinterpret_cast<const TI *>(seg), h, w, ld, t, idx, segs, count, sums, bbox)
-    switch (seg_dtype) {
-    case PXSOM_SEG_U8: PXSOM_CQ_MAP(uint8_t); break;
-    case PXSOM_SEG_I16: PXSOM_CQ_MAP(int16_t); break;
-    case PXSOM_SEG_U16: PXSOM_CQ_MAP(uint16_t); break;
-    case PXSOM_SEG_I32: PXSOM_CQ_MAP(int32_t); break;
-    case PXSOM_SEG_U32: PXSOM_CQ_MAP(uint32_t); break;
-    default: PXSOM_CQ_MAP(int64_t); break;
-    }
-#undef PXSOM_CQ_MAP
+    pxsom::dispatch_label(seg_dtype, [&](auto ti) {
+        typedef decltype(ti) TI;
+        hipLaunchKernelGGL((map_kernel<TI, kStats>), dim3((unsigned)blocks), dim3(256), 0, st,
+                           reinterpret_cast<const TI *>(seg), h, w, ld, t, idx, segs, count, sums, bbox);
+    });
     PXSOM_LAUNCH_CHECK("map_kernel");
     return PXSOM_OK;
 }
@@ -573,8 +502,8 @@ PXSOM_EXPORT int pxsom_cellquant(const void *seg_dev, int seg_dtype, int64_t ld,
                                  void *workspace_dev, size_t workspace_bytes, int flags, void *stream)
 {
     const char *fn = "pxsom_cellquant";
-    if (!label_bytes(seg_dtype)) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad seg_dtype %d", fn, seg_dtype);
-    if (!image_bytes(img_dtype)) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad img_dtype %d", fn, img_dtype);
+    if (!pxsom::is_label_dtype(seg_dtype)) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad seg_dtype %d", fn, seg_dtype);
+    if (!pxsom::is_image_dtype(img_dtype, true)) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad img_dtype %d", fn, img_dtype);
     if (mode < PXSOM_CELLQUANT_TOTAL || mode > PXSOM_CELLQUANT_CENTER)
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad mode %d", fn, mode);
     if (h < 1 || w < 1 || c < 1 || ld < w)
@@ -586,7 +515,7 @@ PXSOM_EXPORT int pxsom_cellquant(const void *seg_dev, int seg_dtype, int64_t ld,
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad cell table or outputs", fn);
     const bool with_nuc = nuc_dev != nullptr;
     if (with_nuc) {
-        if (!label_bytes(nuc_dtype) || ldn < w || n_nuc_keys < 0 || (n_keys > 0 && !nuc_out_dev) ||
+        if (!pxsom::is_label_dtype(nuc_dtype) || ldn < w || n_nuc_keys < 0 || (n_keys > 0 && !nuc_out_dev) ||
             (n_nuc_keys > 0 && (!nuc_keys_dev || nuc_key_min > nuc_key_max)))
             return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad nuclear image, table or output", fn);
         if (nuc_capacity == 0) nuc_capacity = kNucMaxCapacity;
@@ -604,16 +533,11 @@ PXSOM_EXPORT int pxsom_cellquant(const void *seg_dev, int seg_dtype, int64_t ld,
     char *ws = static_cast<char *>(workspace_dev);
     unsigned long long *count = reinterpret_cast<unsigned long long *>(count_dev);
     unsigned long long *sums = reinterpret_cast<unsigned long long *>(sums_dev);
-    {
-        const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n_keys + 255) / 256, (int64_t)pxsom::device_cu_count() * 4));
-        hipLaunchKernelGGL(init_kernel, dim3((unsigned)grid), dim3(256), 0, st, n_keys, count, sums, bbox_dev);
-        PXSOM_LAUNCH_CHECK("init_kernel");
-    }
+    hipLaunchKernelGGL(init_kernel, dim3(pxsom::flat_grid(n_keys, 4)), dim3(256), 0, st, n_keys, count, sums, bbox_dev);
+    PXSOM_LAUNCH_CHECK("init_kernel");
     KeyTable t{keys_dev, nullptr, n_keys, key_min, 0};
     if (L.lut_b) {
-        t.lut = reinterpret_cast<int32_t *>(ws + L.lut);
-        t.lut_size = (int64_t)(L.lut_b / sizeof(int32_t));
-        int rc = build_lut(keys_dev, n_keys, key_min, L.lut_b, reinterpret_cast<int32_t *>(ws + L.lut), st);
+        const int rc = build_lut(t, reinterpret_cast<int32_t *>(ws + L.lut), L.lut_b, st);
         if (rc != PXSOM_OK) return rc;
     }
     int32_t *idx = reinterpret_cast<int32_t *>(ws + L.idx);
@@ -628,9 +552,7 @@ PXSOM_EXPORT int pxsom_cellquant(const void *seg_dev, int seg_dtype, int64_t ld,
             PXSOM_HIP_TRY(hipMemsetAsync(nuc_idx, 0xFF, (size_t)h * w * sizeof(int32_t), st));
         } else {
             if (L.nuc_lut_b) {
-                tn.lut = reinterpret_cast<int32_t *>(ws + L.nuc_lut);
-                tn.lut_size = (int64_t)(L.nuc_lut_b / sizeof(int32_t));
-                rc = build_lut(nuc_keys_dev, n_nuc_keys, nuc_key_min, L.nuc_lut_b, reinterpret_cast<int32_t *>(ws + L.nuc_lut), st);
+                rc = build_lut(tn, reinterpret_cast<int32_t *>(ws + L.nuc_lut), L.nuc_lut_b, st);
                 if (rc != PXSOM_OK) return rc;
             }
             rc = launch_map<false>(nuc_dev, nuc_dtype, h, w, ldn, tn, nuc_idx, nullptr, nullptr, nullptr, st);
@@ -661,12 +583,5 @@ PXSOM_EXPORT int pxsom_cellquant(const void *seg_dev, int seg_dtype, int64_t ld,
         a.off = off;
         a.list = ws + L.list;
     }
-    switch (img_dtype) {
-    case PXSOM_SEG_U8: return launch_walk_typed<uint8_t>(img_dev, a, mode, st);
-    case PXSOM_SEG_I16: return launch_walk_typed<int16_t>(img_dev, a, mode, st);
-    case PXSOM_SEG_U16: return launch_walk_typed<uint16_t>(img_dev, a, mode, st);
-    case PXSOM_SEG_I32: return launch_walk_typed<int32_t>(img_dev, a, mode, st);
-    case PXSOM_SEG_F32: return launch_walk_typed<float>(img_dev, a, mode, st);
-    default: return launch_walk_typed<double>(img_dev, a, mode, st);
-    }
+    return pxsom::dispatch_image<true>(img_dtype, [&](auto ti) { return launch_walk_typed<decltype(ti)>(img_dev, a, mode, st); });
 }

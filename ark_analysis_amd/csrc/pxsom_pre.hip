@@ -4,6 +4,8 @@
 //                                  (/root/reference/src/ark/phenotyping/pixie_preprocessing.py:47-49)
 //   pxsom_gaussian_blur_plane      the same on one [h, w] plane in its own dtype (smooth_channels,
 //                                  pixel_cluster_utils.py:183-230)
+//   pxsom_gaussian_blur_plane_mode the same with a border argument (reflect / nearest) and binary64 planes
+//                                  (the object masks of pxsom_ccl.hip)
 //   pxsom_zero_by_seg              img[seg > 0] = 0 / img[seg == 0] = 0 (filter_with_nuclear_mask, :233-291)
 //   pxsom_rowsum_filter_normalize  row-sum threshold + non-zero filter + row normalisation + compaction
 //                                  (pixie_preprocessing.py:67-75, pixel_cluster_utils.py:126-130)
@@ -21,29 +23,11 @@
 #include <cmath>
 
 #include "pxsom_common.h"
+#include "pxsom_plane.h"
 
 namespace {
 
 #pragma clang fp contract(off)
-
-constexpr int kMaxRadius = 64;
-
-struct Taps {
-    double w[kMaxRadius + 1];  // w[0] centre, w[d] weight at distance d (symmetric kernel)
-    int radius;
-};
-
-// scipy NI_EXTEND_REFLECT: (d c b a | a b c d | d c b a)
-__device__ __forceinline__ int reflect_idx(int i, int len)
-{
-    /* position i of the infinitely reflected line, for any i (the image may be shorter than the kernel radius:
-     * scipy's NI_ExtendLine keeps reflecting, period 2 * len) */
-    if (len == 1) return 0;
-    const int sz2 = 2 * len;
-    int m = i % sz2;
-    if (m < 0) m += sz2;
-    return m < len ? m : sz2 - 1 - m;
-}
 
 // How a blur pass stores its binary64 sums: scipy's correlate1d writes each output line into the output array, i.e. in
 // that array's dtype, and the second pass reads the first pass's output from there.
@@ -70,9 +54,10 @@ struct StoreAs {
 // AXIS 0: along image rows (stride W*C), AXIS 1: along image columns (stride C).
 //
 // Generic form (any radius, tiny images): thread <-> one output element, every tap a coalesced read served by L1 / L2.
+// Off the interior the line is extended by border_idx (`nearest`: scipy's mode "nearest" instead of "reflect").
 template <int AXIS, typename S>
 __global__ __launch_bounds__(256) void blur_pass_kernel(const typename S::E *__restrict__ in, typename S::E *__restrict__ out,
-                                                        int H, int W, int C, Taps taps)
+                                                        int H, int W, int C, Taps taps, int nearest)
 {
     const int64_t total = (int64_t)H * W * C;
     const int64_t wc = (int64_t)W * C;
@@ -86,23 +71,16 @@ __global__ __launch_bounds__(256) void blur_pass_kernel(const typename S::E *__r
         double tmp = (double)in[e] * taps.w[0];
         const bool interior = pos >= taps.radius && pos + taps.radius < len;
         for (int d = taps.radius; d >= 1; d--) {
-            const int lo = interior ? pos - d : reflect_idx(pos - d, len);
-            const int hi = interior ? pos + d : reflect_idx(pos + d, len);
+            const int lo = interior ? pos - d : border_idx(pos - d, len, nearest);
+            const int hi = interior ? pos + d : border_idx(pos + d, len, nearest);
             tmp += ((double)in[base + (int64_t)lo * stride] + (double)in[base + (int64_t)hi * stride]) * taps.w[d];
         }
         out[e] = S::put(tmp);
     }
 }
 
-// Tiles of the two fast forms are dealt to the XCDs in contiguous runs: workgroup b runs on XCD b % 8 (round robin),
-// and every XCD has an L2 of its own -- neighbouring tiles share their halo, so they should meet in the same L2
-// (the generic form above fetched 1.7x / 2.4x the image from HBM per pass: profiles/r03/preprocess.txt).
-__device__ __forceinline__ int64_t xcd_contiguous(int64_t b, int64_t nb)
-{
-    constexpr int kXcds = 8;
-    const int64_t per = (nb + kXcds - 1) / kXcds;
-    return (b % kXcds) * per + b / kXcds;     // may be >= nb: the caller skips those
-}
+// Tiles of the two fast forms are dealt to the XCDs in contiguous runs (xcd_contiguous): the generic form above fetched
+// 1.7x / 2.4x the image from HBM per pass (profiles/r03/preprocess.txt).
 
 // AXIS 0, radius R (the pipeline's sigma = 2: R = 8): thread <-> one image column element (x, c), walking down a strip
 // of rows with the last 2R+1 values of its column in REGISTERS -- every input is read once per strip (coalesced across
@@ -123,7 +101,7 @@ __global__ __launch_bounds__(256) void blur_rows_window_kernel(const double *__r
     const int y0 = (int)strip * TY, y1 = min(y0 + TY, H);
     double win[NW];   // win[i] = in[reflect(y - R + i)] for the output row y being formed
 #pragma unroll
-    for (int i = 0; i < NW; i++) win[i] = in[(int64_t)reflect_idx(y0 - R + i, H) * wc + col];
+    for (int i = 0; i < NW; i++) win[i] = in[(int64_t)border_idx(y0 - R + i, H, 0) * wc + col];
     double w[R + 1];
 #pragma unroll
     for (int d = 0; d <= R; d++) w[d] = taps.w[d];
@@ -137,7 +115,7 @@ __global__ __launch_bounds__(256) void blur_rows_window_kernel(const double *__r
                 for (int d = R; d >= 1; d--) tmp += (win[(u + R - d) % NW] + win[(u + R + d) % NW]) * w[d];
                 out[(int64_t)(y + u) * wc + col] = R32 ? (double)(float)tmp : tmp;
                 // the oldest value (register u) makes room for row y + u + R + 1
-                win[u] = in[(int64_t)reflect_idx(y + u + R + 1, H) * wc + col];
+                win[u] = in[(int64_t)border_idx(y + u + R + 1, H, 0) * wc + col];
             }
         }
     }
@@ -164,7 +142,7 @@ __global__ __launch_bounds__(256) void blur_cols_lds_kernel(const double *__rest
         // pixel index floor(e / C) reflected, channel kept
         int64_t px = e >= 0 ? e / C : -((-e + C - 1) / C);
         const int ch = (int)(e - px * C);
-        blur_tile[i] = px >= W + R ? 0.0 : row[(int64_t)reflect_idx((int)px, W) * C + ch];   // (past the tile's last real output: unused)
+        blur_tile[i] = px >= W + R ? 0.0 : row[(int64_t)border_idx((int)px, W, 0) * C + ch];   // (past the tile's last real output: unused)
     }
     __syncthreads();
     double w[R + 1];
@@ -631,10 +609,7 @@ PXSOM_EXPORT int pxsom_gaussian_blur_hwc(double *img_dev, double *tmp_dev, int h
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_gaussian_blur_hwc: bad arguments");
     if (radius < 0 || radius > kMaxRadius)
         return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_gaussian_blur_hwc: radius %d outside [0, %d]", radius, kMaxRadius);
-    Taps taps;
-    taps.radius = radius;
-    for (int d = 0; d <= radius; d++) taps.w[d] = weights_host[radius + d];  // symmetric: w[r+d] == w[r-d]
-    for (int d = radius + 1; d <= kMaxRadius; d++) taps.w[d] = 0.0;
+    const Taps taps = fill_taps(weights_host, radius);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)h * w * c;
     const int64_t wc = (int64_t)w * c;
@@ -660,54 +635,64 @@ PXSOM_EXPORT int pxsom_gaussian_blur_hwc(double *img_dev, double *tmp_dev, int h
         PXSOM_LAUNCH_CHECK("blur_rows_window_kernel / blur_cols_lds_kernel");
         return PXSOM_OK;
     }
-    const int grid = (int)std::min<int64_t>((total + 255) / 256, (int64_t)pxsom::device_cu_count() * 16);
+    const int grid = pxsom::flat_grid(total);
     if (f32_semantics) {
-        hipLaunchKernelGGL((blur_pass_kernel<0, StoreF64R32>), dim3(grid), dim3(256), 0, st, img_dev, tmp_dev, h, w, c, taps);
-        hipLaunchKernelGGL((blur_pass_kernel<1, StoreF64R32>), dim3(grid), dim3(256), 0, st, tmp_dev, img_dev, h, w, c, taps);
+        hipLaunchKernelGGL((blur_pass_kernel<0, StoreF64R32>), dim3(grid), dim3(256), 0, st, img_dev, tmp_dev, h, w, c, taps, 0);
+        hipLaunchKernelGGL((blur_pass_kernel<1, StoreF64R32>), dim3(grid), dim3(256), 0, st, tmp_dev, img_dev, h, w, c, taps, 0);
     } else {
-        hipLaunchKernelGGL((blur_pass_kernel<0, StoreF64>), dim3(grid), dim3(256), 0, st, img_dev, tmp_dev, h, w, c, taps);
-        hipLaunchKernelGGL((blur_pass_kernel<1, StoreF64>), dim3(grid), dim3(256), 0, st, tmp_dev, img_dev, h, w, c, taps);
+        hipLaunchKernelGGL((blur_pass_kernel<0, StoreF64>), dim3(grid), dim3(256), 0, st, img_dev, tmp_dev, h, w, c, taps, 0);
+        hipLaunchKernelGGL((blur_pass_kernel<1, StoreF64>), dim3(grid), dim3(256), 0, st, tmp_dev, img_dev, h, w, c, taps, 0);
     }
     PXSOM_LAUNCH_CHECK("blur_pass_kernel");
     return PXSOM_OK;
 }
 
 namespace {
-template <typename T>
-void launch_plane_blur(const void *in, void *out, void *tmp, int h, int w, const Taps &taps, int grid, hipStream_t st)
+// both passes of one [h, w] plane in its own dtype (an image dtype, f64 included); the caller has checked every argument
+int launch_plane_blur(const char *fn, int dtype, int border, const void *in, void *out, void *tmp, int h, int w,
+                      const double *weights_host, int radius, hipStream_t st)
 {
-    hipLaunchKernelGGL((blur_pass_kernel<0, StoreAs<T>>), dim3(grid), dim3(256), 0, st, static_cast<const T *>(in),
-                       static_cast<T *>(tmp), h, w, 1, taps);
-    hipLaunchKernelGGL((blur_pass_kernel<1, StoreAs<T>>), dim3(grid), dim3(256), 0, st, static_cast<const T *>(tmp),
-                       static_cast<T *>(out), h, w, 1, taps);
+    if (radius < 0 || radius > kMaxRadius)
+        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "%s: radius %d outside [0, %d]", fn, radius, kMaxRadius);
+    const Taps taps = fill_taps(weights_host, radius);
+    const int grid = pxsom::flat_grid((int64_t)h * w), nearest = border == PXSOM_BLUR_NEAREST;
+    pxsom::dispatch_image<true>(dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((blur_pass_kernel<0, StoreAs<T>>), dim3(grid), dim3(256), 0, st, static_cast<const T *>(in),
+                           static_cast<T *>(tmp), h, w, 1, taps, nearest);
+        hipLaunchKernelGGL((blur_pass_kernel<1, StoreAs<T>>), dim3(grid), dim3(256), 0, st, static_cast<const T *>(tmp),
+                           static_cast<T *>(out), h, w, 1, taps, nearest);
+    });
+    PXSOM_LAUNCH_CHECK("blur_pass_kernel (plane)");
+    return PXSOM_OK;
 }
 }  // namespace
 
 PXSOM_EXPORT int pxsom_gaussian_blur_plane(const void *in_dev, void *out_dev, void *tmp_dev, int h, int w, int dtype,
                                            const double *weights_host, int radius, void *stream)
 {
+    const char *fn = "pxsom_gaussian_blur_plane";
     if (!in_dev || !out_dev || !tmp_dev || !weights_host || h < 1 || w < 1 || tmp_dev == in_dev || tmp_dev == out_dev)
-        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_gaussian_blur_plane: bad arguments");
-    if (dtype != PXSOM_SEG_U8 && dtype != PXSOM_SEG_I16 && dtype != PXSOM_SEG_U16 && dtype != PXSOM_SEG_I32 &&
-        dtype != PXSOM_SEG_F32)
-        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_gaussian_blur_plane: dtype %d is not u8 / i16 / u16 / i32 / f32", dtype);
-    if (radius < 0 || radius > kMaxRadius)
-        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_gaussian_blur_plane: radius %d outside [0, %d]", radius, kMaxRadius);
-    Taps taps;
-    taps.radius = radius;
-    for (int d = 0; d <= radius; d++) taps.w[d] = weights_host[radius + d];
-    for (int d = radius + 1; d <= kMaxRadius; d++) taps.w[d] = 0.0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int grid = (int)std::min<int64_t>(((int64_t)h * w + 255) / 256, (int64_t)pxsom::device_cu_count() * 16);
-    switch (dtype) {
-    case PXSOM_SEG_U8: launch_plane_blur<uint8_t>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
-    case PXSOM_SEG_I16: launch_plane_blur<int16_t>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
-    case PXSOM_SEG_U16: launch_plane_blur<uint16_t>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
-    case PXSOM_SEG_I32: launch_plane_blur<int32_t>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
-    default: launch_plane_blur<float>(in_dev, out_dev, tmp_dev, h, w, taps, grid, st); break;
-    }
-    PXSOM_LAUNCH_CHECK("blur_pass_kernel (plane)");
-    return PXSOM_OK;
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad arguments", fn);
+    if (!pxsom::is_image_dtype(dtype, false))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: dtype %d is not u8 / i16 / u16 / i32 / f32", fn, dtype);
+    return launch_plane_blur(fn, dtype, PXSOM_BLUR_REFLECT, in_dev, out_dev, tmp_dev, h, w, weights_host, radius,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
+// the same with a border argument (reflect / nearest) and binary64 planes (the object masks of K16)
+PXSOM_EXPORT int pxsom_gaussian_blur_plane_mode(const void *in_dev, void *out_dev, void *tmp_dev, int h, int w, int dtype,
+                                                const double *weights_host, int radius, int border, void *stream)
+{
+    const char *fn = "pxsom_gaussian_blur_plane_mode";
+    if (!in_dev || !out_dev || !tmp_dev || !weights_host || h < 1 || w < 1 || tmp_dev == in_dev || tmp_dev == out_dev)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad arguments", fn);
+    if (!pxsom::is_image_dtype(dtype, true))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: dtype %d is not u8 / i16 / u16 / i32 / f32 / f64", fn, dtype);
+    if (border != PXSOM_BLUR_REFLECT && border != PXSOM_BLUR_NEAREST)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: border %d", fn, border);
+    return launch_plane_blur(fn, dtype, border, in_dev, out_dev, tmp_dev, h, w, weights_host, radius,
+                             reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- img[i] = 0 where seg[i] > 0 (exclude) or seg[i] == 0 (include): filter_with_nuclear_mask ----
@@ -722,22 +707,6 @@ __global__ __launch_bounds__(256) void zero_by_seg_kernel(TI *__restrict__ img, 
     }
 }
 
-template <typename TI>
-void launch_zero_by_seg(void *img, const void *seg, int seg_dtype, int64_t n, int exclude, int grid, hipStream_t st)
-{
-    TI *im = static_cast<TI *>(img);
-#define PXSOM_ZERO_BY(TS) \
-    hipLaunchKernelGGL((zero_by_seg_kernel<TI, TS>), dim3(grid), dim3(256), 0, st, im, static_cast<const TS *>(seg), n, exclude)
-    switch (seg_dtype) {
-    case PXSOM_SEG_U8: PXSOM_ZERO_BY(uint8_t); break;
-    case PXSOM_SEG_I16: PXSOM_ZERO_BY(int16_t); break;
-    case PXSOM_SEG_U16: PXSOM_ZERO_BY(uint16_t); break;
-    case PXSOM_SEG_I32: PXSOM_ZERO_BY(int32_t); break;
-    case PXSOM_SEG_U32: PXSOM_ZERO_BY(uint32_t); break;
-    default: PXSOM_ZERO_BY(int64_t); break;
-    }
-#undef PXSOM_ZERO_BY
-}
 }  // namespace
 
 PXSOM_EXPORT int pxsom_zero_by_seg(void *img_dev, int img_dtype, const void *seg_dev, int seg_dtype, int64_t n,
@@ -745,21 +714,21 @@ PXSOM_EXPORT int pxsom_zero_by_seg(void *img_dev, int img_dtype, const void *seg
 {
     if (n < 0 || (n > 0 && (!img_dev || !seg_dev)) || (exclude != 0 && exclude != 1))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_zero_by_seg: bad arguments");
-    if (img_dtype != PXSOM_SEG_U8 && img_dtype != PXSOM_SEG_I16 && img_dtype != PXSOM_SEG_U16 && img_dtype != PXSOM_SEG_I32 &&
-        img_dtype != PXSOM_SEG_F32)
+    if (!pxsom::is_image_dtype(img_dtype, false))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_zero_by_seg: image dtype %d is not u8 / i16 / u16 / i32 / f32", img_dtype);
-    if (seg_dtype < PXSOM_SEG_U8 || seg_dtype > PXSOM_SEG_I64)
+    if (!pxsom::is_label_dtype(seg_dtype))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_zero_by_seg: segmentation dtype %d is not u8 .. i64", seg_dtype);
     if (n == 0) return PXSOM_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)pxsom::device_cu_count() * 16);
-    switch (img_dtype) {
-    case PXSOM_SEG_U8: launch_zero_by_seg<uint8_t>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
-    case PXSOM_SEG_I16: launch_zero_by_seg<int16_t>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
-    case PXSOM_SEG_U16: launch_zero_by_seg<uint16_t>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
-    case PXSOM_SEG_I32: launch_zero_by_seg<int32_t>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
-    default: launch_zero_by_seg<float>(img_dev, seg_dev, seg_dtype, n, exclude, grid, st); break;
-    }
+    const int grid = pxsom::flat_grid(n);
+    pxsom::dispatch_image<false>(img_dtype, [&](auto ti) {
+        pxsom::dispatch_label(seg_dtype, [&](auto ts) {
+            typedef decltype(ti) TI;
+            typedef decltype(ts) TS;
+            hipLaunchKernelGGL((zero_by_seg_kernel<TI, TS>), dim3(grid), dim3(256), 0, st, static_cast<TI *>(img_dev),
+                               static_cast<const TS *>(seg_dev), n, exclude);
+        });
+    });
     PXSOM_LAUNCH_CHECK("zero_by_seg_kernel");
     return PXSOM_OK;
 }
@@ -827,8 +796,7 @@ PXSOM_EXPORT int pxsom_normalize_columns(const double *x_dev, int64_t n, int c, 
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_normalize_columns: bad arguments");
     if (n == 0) return PXSOM_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int grid = (int)std::min<int64_t>((n * c + 255) / 256, (int64_t)pxsom::device_cu_count() * 16);
-    hipLaunchKernelGGL(normalize_columns_kernel, dim3(grid), dim3(256), 0, st, x_dev, n, c, ldx, norm_dev, out_dev, ldo);
+    hipLaunchKernelGGL(normalize_columns_kernel, dim3(pxsom::flat_grid(n * c)), dim3(256), 0, st, x_dev, n, c, ldx, norm_dev, out_dev, ldo);
     PXSOM_LAUNCH_CHECK("normalize_columns_kernel");
     return PXSOM_OK;
 }
@@ -935,8 +903,7 @@ int scaled_rowsum(const char *fn, const F *img_dev, int64_t n, int c, int64_t ld
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad arguments (c <= 128)", fn);
     if (n == 0) return PXSOM_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int64_t grid = std::min<int64_t>((n + 255) / 256, (int64_t)pxsom::device_cu_count() * 16);
-    hipLaunchKernelGGL(scaled_rowsum_kernel<F>, dim3((unsigned)grid), dim3(256), 0, st, img_dev, n, c, ldx, norm_dev,
+    hipLaunchKernelGGL(scaled_rowsum_kernel<F>, dim3(pxsom::flat_grid(n)), dim3(256), 0, st, img_dev, n, c, ldx, norm_dev,
                        out_dev);
     PXSOM_LAUNCH_CHECK("scaled_rowsum_kernel");
     return PXSOM_OK;
@@ -1021,14 +988,13 @@ PXSOM_EXPORT int pxsom_cluster_mask(const int64_t *row_index_dev, const int64_t 
     const int64_t pixels = (int64_t)h * w;
     PXSOM_HIP_TRY(hipMemsetAsync(workspace_dev, 0xFF, need, st));  // every winner = -1
     PXSOM_HIP_TRY(hipMemsetAsync(status_dev, 0, sizeof(int32_t), st));
-    const int64_t cap = (int64_t)pxsom::device_cu_count() * 16;
     long long *winner = reinterpret_cast<long long *>(workspace_dev);
     if (n > 0) {
-        hipLaunchKernelGGL(mask_winner_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, cap)), dim3(256), 0, st,
+        hipLaunchKernelGGL(mask_winner_kernel, dim3(pxsom::flat_grid(n)), dim3(256), 0, st,
                            row_index_dev, column_index_dev, labels_dev, n, lut_dev, lut_size, h, w, winner, status_dev);
         PXSOM_LAUNCH_CHECK("mask_winner_kernel");
     }
-    hipLaunchKernelGGL(mask_resolve_kernel, dim3((unsigned)std::min<int64_t>((pixels + 255) / 256, cap)), dim3(256), 0,
+    hipLaunchKernelGGL(mask_resolve_kernel, dim3(pxsom::flat_grid(pixels)), dim3(256), 0,
                        st, labels_dev, lut_dev, lut_size, pixels, winner, mask_dev);
     PXSOM_LAUNCH_CHECK("mask_resolve_kernel");
     return PXSOM_OK;

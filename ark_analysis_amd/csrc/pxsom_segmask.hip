@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "pxsom_common.h"
+#include "pxsom_keytable.h"
 
 namespace {
 
@@ -23,7 +24,6 @@ constexpr int kWaveCols = 256;       // 64 lanes x 4 pixels
 constexpr int kRowsPerWave = 4;
 constexpr int kWaves = 4;
 constexpr int kBlockRows = kRowsPerWave * kWaves;
-constexpr int64_t kDenseMaxEntries = int64_t(1) << 24;   // 64 MB of int32 at most
 
 template <typename T>
 struct Vec4 {
@@ -67,39 +67,22 @@ __device__ __forceinline__ void load_row(const TI *__restrict__ seg, int64_t ld,
 
 template <typename TV>
 struct Table {
-    const int32_t *keys;
+    KeyTable k;              // k.n_keys < 0: no lookup
     const TV *values;
-    const int32_t *lut;      // dense route: index of key_min + i in keys, -1 when absent; nullptr: binary search
-    int64_t n_keys;          // < 0: no lookup
-    int32_t key_min;
-    int64_t lut_size;
     TV unassigned;
 };
 
 template <typename TV, typename TI>
 __device__ __forceinline__ TV lookup(const Table<TV> &t, TI label)
 {
-    const int32_t key = (int32_t)(int64_t)label;            // numpy astype(np.int32): two's-complement wrap
-    int64_t idx = -1;
-    if (t.lut) {
-        const int64_t d = (int64_t)key - t.key_min;
-        if (d >= 0 && d < t.lut_size) idx = t.lut[d];
-    } else {
-        int64_t lo = 0, hi = t.n_keys;                      // first key >= `key`
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (t.keys[mid] < key) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo < t.n_keys && t.keys[lo] == key) idx = lo;
-    }
+    const int64_t idx = find_key(t.k, (int32_t)(int64_t)label);   // numpy astype(np.int32): two's-complement wrap
     return idx >= 0 ? t.values[idx] : t.unassigned;
 }
 
 template <typename TI, typename TO, typename TV>
 __device__ __forceinline__ TO finish(const Table<TV> &t, TI label)
 {
-    if (t.n_keys < 0) return (TO)label;   // no lookup: the (eroded) label, cast as numpy casts
+    if (t.k.n_keys < 0) return (TO)label;   // no lookup: the (eroded) label, cast as numpy casts
     return (TO)lookup<TV, TI>(t, label);
 }
 
@@ -184,38 +167,14 @@ __global__ __launch_bounds__(256) void segmask_kernel(const TI *__restrict__ seg
     }
 }
 
-__global__ __launch_bounds__(256) void lut_scatter_kernel(const int32_t *__restrict__ keys, int64_t n, int32_t key_min,
-                                                          int64_t lut_size, int32_t *__restrict__ lut)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t d = (int64_t)keys[i] - key_min;
-        if (d >= 0 && d < lut_size) lut[d] = (int32_t)i;
-    }
-}
-
-int dtype_bytes(int dt)
-{
-    switch (dt) {
-    case PXSOM_SEG_U8: return 1;
-    case PXSOM_SEG_I16: case PXSOM_SEG_U16: return 2;
-    case PXSOM_SEG_I32: case PXSOM_SEG_U32: return 4;
-    case PXSOM_SEG_I64: case PXSOM_SEG_F64: return 8;
-    default: return 0;
-    }
-}
-
 struct Launch {
     const void *seg;
     int h, w;
     int64_t ld;
     int erode_mode, conn8;
     int64_t background;
-    const int32_t *keys;
+    KeyTable keys;
     const void *values;
-    const int32_t *lut;
-    int64_t n_keys;
-    int32_t key_min;
-    int64_t lut_size;
     double unassigned;
     void *out;
     int64_t ldo;
@@ -226,14 +185,7 @@ template <typename TI, typename TO>
 int launch_typed(const Launch &a)
 {
     typedef typename std::conditional<std::is_same<TO, double>::value, double, int32_t>::type TV;
-    Table<TV> t;
-    t.keys = a.keys;
-    t.values = reinterpret_cast<const TV *>(a.values);
-    t.lut = a.lut;
-    t.n_keys = a.n_keys;
-    t.key_min = a.key_min;
-    t.lut_size = a.lut_size;
-    t.unassigned = (TV)a.unassigned;
+    const Table<TV> t{a.keys, reinterpret_cast<const TV *>(a.values), (TV)a.unassigned};
     const auto aligned = [](const void *p, int64_t stride, size_t vbytes) {
         return (reinterpret_cast<uintptr_t>(p) % vbytes) == 0 && stride % 4 == 0;
     };
@@ -261,11 +213,7 @@ int launch_in(const Launch &a, int out_dtype, int seg_dtype)
 
 PXSOM_EXPORT size_t pxsom_segmask_workspace_bytes(int64_t n_keys, int32_t key_min, int32_t key_max)
 {
-    if (n_keys <= 0 || key_max < key_min) return 0;
-    const int64_t range = (int64_t)key_max - key_min + 1;
-    // dense when the LUT is at most 64 MB and not far sparser than the table (16 slots a key + 64 Ki)
-    if (range > kDenseMaxEntries || range > 16 * n_keys + 65536) return 0;
-    return (size_t)range * sizeof(int32_t);
+    return pxsom::dense_lut_bytes(n_keys, key_min, key_max);
 }
 
 PXSOM_EXPORT int pxsom_segmask(const void *seg_dev, int seg_dtype, int h, int w, int64_t ld, int erode_mode,
@@ -275,7 +223,7 @@ PXSOM_EXPORT int pxsom_segmask(const void *seg_dev, int seg_dtype, int h, int w,
                                void *stream)
 {
     const char *fn = "pxsom_segmask";
-    if (seg_dtype < PXSOM_SEG_U8 || seg_dtype > PXSOM_SEG_I64)
+    if (!pxsom::is_label_dtype(seg_dtype))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad seg_dtype %d", fn, seg_dtype);
     if (out_dtype != seg_dtype && out_dtype != PXSOM_SEG_I16 && out_dtype != PXSOM_SEG_I32 && out_dtype != PXSOM_SEG_F64)
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad out_dtype %d", fn, out_dtype);
@@ -296,8 +244,8 @@ PXSOM_EXPORT int pxsom_segmask(const void *seg_dev, int seg_dtype, int h, int w,
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: unassigned %g is not an int32 value", fn, unassigned);
     if (erode_mode != PXSOM_SEG_ERODE_NONE) {   // erosion reads neighbours another block may already have written
         const char *s0 = static_cast<const char *>(seg_dev), *o0 = static_cast<const char *>(out_dev);
-        const char *s1 = s0 + ((int64_t)(h - 1) * ld + w) * dtype_bytes(seg_dtype);
-        const char *o1 = o0 + ((int64_t)(h - 1) * ldo + w) * dtype_bytes(out_dtype);
+        const char *s1 = s0 + ((int64_t)(h - 1) * ld + w) * pxsom::plane_dtype_bytes(seg_dtype);
+        const char *o1 = o0 + ((int64_t)(h - 1) * ldo + w) * pxsom::plane_dtype_bytes(out_dtype);
         if (s0 < o1 && o0 < s1) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps seg under erosion", fn);
     }
     const size_t need = n_keys > 0 && !(flags & PXSOM_SEGMASK_FORCE_SEARCH)
@@ -313,32 +261,15 @@ PXSOM_EXPORT int pxsom_segmask(const void *seg_dev, int seg_dtype, int h, int w,
     a.erode_mode = erode_mode;
     a.conn8 = connectivity >= 2;
     a.background = background;
-    a.keys = keys_dev;
+    a.keys = KeyTable{keys_dev, nullptr, n_keys < 0 ? -1 : n_keys, key_min, 0};
     a.values = values_dev;
-    a.lut = nullptr;
-    a.n_keys = n_keys < 0 ? -1 : n_keys;
-    a.key_min = key_min;
-    a.lut_size = 0;
     a.unassigned = unassigned;
     a.out = out_dev;
     a.ldo = ldo;
     a.st = reinterpret_cast<hipStream_t>(stream);
     if (need > 0) {
-        int32_t *lut = static_cast<int32_t *>(workspace_dev);
-        a.lut = lut;
-        a.lut_size = (int64_t)key_max - key_min + 1;
-        PXSOM_HIP_TRY(hipMemsetAsync(lut, 0xFF, need, a.st));   // every slot -1: absent
-        const int64_t grid = std::min<int64_t>((n_keys + 255) / 256, (int64_t)pxsom::device_cu_count() * 4);
-        hipLaunchKernelGGL(lut_scatter_kernel, dim3((unsigned)grid), dim3(256), 0, a.st, keys_dev, n_keys, key_min,
-                           a.lut_size, lut);
-        PXSOM_LAUNCH_CHECK("lut_scatter_kernel");
+        const int rc = build_lut(a.keys, static_cast<int32_t *>(workspace_dev), need, a.st);
+        if (rc != PXSOM_OK) return rc;
     }
-    switch (seg_dtype) {
-    case PXSOM_SEG_U8: return launch_in<uint8_t>(a, out_dtype, seg_dtype);
-    case PXSOM_SEG_I16: return launch_in<int16_t>(a, out_dtype, seg_dtype);
-    case PXSOM_SEG_U16: return launch_in<uint16_t>(a, out_dtype, seg_dtype);
-    case PXSOM_SEG_I32: return launch_in<int32_t>(a, out_dtype, seg_dtype);
-    case PXSOM_SEG_U32: return launch_in<uint32_t>(a, out_dtype, seg_dtype);
-    default: return launch_in<int64_t>(a, out_dtype, seg_dtype);
-    }
+    return pxsom::dispatch_label(seg_dtype, [&](auto ti) { return launch_in<decltype(ti)>(a, out_dtype, seg_dtype); });
 }

@@ -673,12 +673,8 @@ def segmentation_mask(seg: torch.Tensor, erode: Optional[str] = None, connectivi
     if out_dtype != seg.dtype and out_dtype not in (torch.int16, torch.int32, torch.float64):
         raise ValueError("out_dtype must be int16, int32, float64 or the image's dtype")
     code_out = SEG_F64 if out_dtype == torch.float64 else SEG_DTYPES[out_dtype]
-    if out is None:
-        out = torch.empty((h, w), dtype=out_dtype, device=seg.device)
-    elif out.shape != (h, w) or out.dtype != out_dtype or not out.is_cuda or (w > 1 and out.stride(1) != 1):
-        raise ValueError("out must be a [H, W] HBM tensor of out_dtype with contiguous rows")
-    ld = seg.stride(0) if h > 1 else w
-    ldo = out.stride(0) if h > 1 else w
+    out = _rows_plane(out, h, w, out_dtype, seg.device, "out")
+    ld, ldo = _ld(seg), _ld(out)
     lib = _capi.lib()
     if table is None:
         keys = values = None
@@ -712,51 +708,12 @@ def check_blur_sigma(sigma: float) -> None:
                                   "(sigma < %g, radius <= %d)" % (sigma, BLUR_SIGMA_LIMIT, BLUR_MAX_RADIUS))
 
 
-def gaussian_blur_plane(plane: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None,
-                        tmp: Optional[torch.Tensor] = None, mode: str = "reflect") -> torch.Tensor:
-    """scipy.ndimage.gaussian_filter(plane, sigma, mode=mode) of a contiguous ``[H, W]`` HBM plane in its own dtype (uint8,
-    int16, uint16, int32, float32 or float64): each pass stored in that dtype, as scipy stores it.  sigma <= 1e-15 skips
-    both axes (scipy's rule): the result is a copy.  ``out`` may be ``plane`` itself.  ``mode``: scipy's border, "reflect"
-    (the default) or "nearest".  The default mode on the five dtypes up to float32 is pxsom_gaussian_blur_plane, route and
-    bits as before the keyword existed; "nearest", and float64 planes (which this function used to refuse) under either
-    mode, go to pxsom_gaussian_blur_plane_mode."""
-    if mode not in BLUR_MODES:
-        raise ValueError("mode must be 'reflect' or 'nearest', got %r" % (mode,))
-    if mode != "reflect" or plane.dtype == torch.float64:
-        return gaussian_blur_plane_mode(plane, sigma, mode, out=out, tmp=tmp)
-    if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in PLANE_DTYPES:
-        raise ValueError("plane must be a contiguous 2-D uint8 / int16 / uint16 / int32 / float32 / float64 HBM tensor")
-    h, w = plane.shape
-    if h == 0 or w == 0:
-        raise ValueError("plane must not be empty")
-    check_blur_sigma(sigma)
-    if out is None:
-        out = torch.empty_like(plane)
-    elif out.shape != plane.shape or out.dtype != plane.dtype or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("out must be a contiguous HBM tensor of the plane's shape and dtype")
-    if float(sigma) <= 1e-15:
-        if out.data_ptr() != plane.data_ptr():
-            out.copy_(plane)
-        return out
-    if tmp is None:
-        tmp = torch.empty_like(plane)
-    elif tmp.shape != plane.shape or tmp.dtype != plane.dtype or not tmp.is_cuda or not tmp.is_contiguous():
-        raise ValueError("tmp must be a contiguous HBM tensor of the plane's shape and dtype")
-    weights, radius = gaussian_kernel1d(float(sigma))
-    rc = _capi.lib().pxsom_gaussian_blur_plane(plane.data_ptr(), out.data_ptr(), tmp.data_ptr(), h, w,
-                                               PLANE_DTYPES[plane.dtype], weights.ctypes.data, radius, _capi.stream_ptr())
-    _capi.check(rc, "pxsom_gaussian_blur_plane")
-    return out
-
-
 BLUR_MODES = {"reflect": 0, "nearest": 1}          # include/pxsom.h PXSOM_BLUR_REFLECT / PXSOM_BLUR_NEAREST
 PLANE_MODE_DTYPES = {**PLANE_DTYPES, torch.float64: 6}
 
 
-def gaussian_blur_plane_mode(plane: torch.Tensor, sigma: float, mode: str, out: Optional[torch.Tensor] = None,
-                             tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """scipy.ndimage.gaussian_filter(plane, sigma, mode=mode) through pxsom_gaussian_blur_plane_mode: the plane blur of
-    :func:`gaussian_blur_plane` with the border "reflect" or "nearest" and float64 planes beside the others."""
+def _blur_plane(plane: torch.Tensor, sigma: float, mode: str, out, tmp, mode_entry: bool) -> torch.Tensor:
+    """The body of both plane blurs; ``mode_entry``: through pxsom_gaussian_blur_plane_mode."""
     if mode not in BLUR_MODES:
         raise ValueError("mode must be 'reflect' or 'nearest', got %r" % (mode,))
     if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in PLANE_MODE_DTYPES:
@@ -765,24 +722,39 @@ def gaussian_blur_plane_mode(plane: torch.Tensor, sigma: float, mode: str, out: 
     if h == 0 or w == 0:
         raise ValueError("plane must not be empty")
     check_blur_sigma(sigma)
-    if out is None:
-        out = torch.empty_like(plane)
-    elif out.shape != plane.shape or out.dtype != plane.dtype or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("out must be a contiguous HBM tensor of the plane's shape and dtype")
+    out = _like_plane(out, plane, "out")
     if float(sigma) <= 1e-15:
         if out.data_ptr() != plane.data_ptr():
             out.copy_(plane)
         return out
-    if tmp is None:
-        tmp = torch.empty_like(plane)
-    elif tmp.shape != plane.shape or tmp.dtype != plane.dtype or not tmp.is_cuda or not tmp.is_contiguous():
-        raise ValueError("tmp must be a contiguous HBM tensor of the plane's shape and dtype")
+    tmp = _like_plane(tmp, plane, "tmp")
     weights, radius = gaussian_kernel1d(float(sigma))
-    rc = _capi.lib().pxsom_gaussian_blur_plane_mode(plane.data_ptr(), out.data_ptr(), tmp.data_ptr(), h, w,
-                                                    PLANE_MODE_DTYPES[plane.dtype], weights.ctypes.data, radius,
-                                                    BLUR_MODES[mode], _capi.stream_ptr())
-    _capi.check(rc, "pxsom_gaussian_blur_plane_mode")
+    args = (plane.data_ptr(), out.data_ptr(), tmp.data_ptr(), h, w, PLANE_MODE_DTYPES[plane.dtype], weights.ctypes.data, radius)
+    if mode_entry:
+        rc = _capi.lib().pxsom_gaussian_blur_plane_mode(*args, BLUR_MODES[mode], _capi.stream_ptr())
+        _capi.check(rc, "pxsom_gaussian_blur_plane_mode")
+    else:
+        rc = _capi.lib().pxsom_gaussian_blur_plane(*args, _capi.stream_ptr())
+        _capi.check(rc, "pxsom_gaussian_blur_plane")
     return out
+
+
+def gaussian_blur_plane(plane: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None,
+                        tmp: Optional[torch.Tensor] = None, mode: str = "reflect") -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(plane, sigma, mode=mode) of a contiguous ``[H, W]`` HBM plane in its own dtype (uint8,
+    int16, uint16, int32, float32 or float64): each pass stored in that dtype, as scipy stores it.  sigma <= 1e-15 skips
+    both axes (scipy's rule): the result is a copy.  ``out`` may be ``plane`` itself.  ``mode``: scipy's border, "reflect"
+    (the default) or "nearest".  The default mode on the five dtypes up to float32 is pxsom_gaussian_blur_plane, route and
+    bits as before the keyword existed; "nearest", and float64 planes (which this function used to refuse) under either
+    mode, go to pxsom_gaussian_blur_plane_mode."""
+    return _blur_plane(plane, sigma, mode, out, tmp, mode != "reflect" or plane.dtype == torch.float64)
+
+
+def gaussian_blur_plane_mode(plane: torch.Tensor, sigma: float, mode: str, out: Optional[torch.Tensor] = None,
+                             tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(plane, sigma, mode=mode) through pxsom_gaussian_blur_plane_mode: the plane blur of
+    :func:`gaussian_blur_plane` with the border "reflect" or "nearest" and float64 planes beside the others."""
+    return _blur_plane(plane, sigma, mode, out, tmp, True)
 
 
 # ---- object masks (K16): labelling, the area passes, the foreground predicates ----------------------------------------
@@ -801,11 +773,25 @@ def _binary_plane(fg: torch.Tensor, what: str) -> torch.Tensor:
     return fg.view(torch.uint8) if fg.dtype == torch.bool else fg
 
 
-def _label_plane(t: Optional[torch.Tensor], h: int, w: int, device, what: str) -> torch.Tensor:
+def _rows_plane(t: Optional[torch.Tensor], h: int, w: int, dtype, device, what: str) -> torch.Tensor:
+    """``t``, checked to be a ``[h, w]`` HBM plane of ``dtype`` with contiguous rows (any row stride), or a new one."""
     if t is None:
-        return torch.empty((h, w), dtype=torch.int32, device=device)
-    if t.shape != (h, w) or t.dtype != torch.int32 or not t.is_cuda or (w > 1 and t.stride(1) != 1):
-        raise ValueError("%s must be a [H, W] int32 HBM tensor with contiguous rows" % what)
+        return torch.empty((h, w), dtype=dtype, device=device)
+    if t.shape != (h, w) or t.dtype != dtype or not t.is_cuda or (w > 1 and t.stride(1) != 1):
+        raise ValueError("%s must be a [H, W] %s HBM tensor with contiguous rows" % (what, str(dtype).replace("torch.", "")))
+    return t
+
+
+def _label_plane(t: Optional[torch.Tensor], h: int, w: int, device, what: str) -> torch.Tensor:
+    return _rows_plane(t, h, w, torch.int32, device, what)
+
+
+def _like_plane(t: Optional[torch.Tensor], plane: torch.Tensor, what: str) -> torch.Tensor:
+    """``t``, checked to be a contiguous HBM tensor of the plane's shape and dtype, or a new one."""
+    if t is None:
+        return torch.empty_like(plane)
+    if t.shape != plane.shape or t.dtype != plane.dtype or not t.is_cuda or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous HBM tensor of the plane's shape and dtype" % what)
     return t
 
 
@@ -861,10 +847,7 @@ def components_select(labels: torch.Tensor, areas: torch.Tensor, mode: str, fg: 
         fg = _binary_plane(fg, "fg")
         if fg.shape != (h, w):
             raise ValueError("fg and labels must have one shape")
-        if out is None:
-            out = torch.empty((h, w), dtype=torch.uint8, device=labels.device)
-        elif out.shape != (h, w) or out.dtype != torch.uint8 or not out.is_cuda or (w > 1 and out.stride(1) != 1):
-            raise ValueError("out must be a [H, W] uint8 HBM tensor with contiguous rows")
+        out = _rows_plane(out, h, w, torch.uint8, labels.device, "out")
         args = (SELECT_FILL, fg.data_ptr(), _ld(fg), 0, max(-lim, min(lim, int(area_threshold))))
     else:
         out = _label_plane(out, h, w, labels.device, "out")
@@ -885,9 +868,10 @@ def binarize_plane(plane: torch.Tensor, mode: int = BIN_POSITIVE, level: float =
         raise ValueError("plane must be a contiguous 2-D float32 / float64 HBM tensor")
     if plane.numel() == 0:
         raise ValueError("plane must not be empty")
-    if mode == BIN_LOCAL and (local is None or local.shape != plane.shape or local.dtype != plane.dtype
-                              or not local.is_cuda or not local.is_contiguous()):
-        raise ValueError("local must be a contiguous HBM plane of the plane's shape and dtype")
+    if mode == BIN_LOCAL:
+        if local is None:
+            raise ValueError("BIN_LOCAL needs the local plane")
+        local = _like_plane(local, plane, "local")
     h, w = plane.shape
     out = torch.empty((h, w), dtype=torch.uint8, device=plane.device)
     rc = _capi.lib().pxsom_binarize_plane(plane.data_ptr(), PLANE_MODE_DTYPES[plane.dtype], h, w, int(mode), float(level),
@@ -967,6 +951,16 @@ class AssignSumsWorkspace:
 TABLES_SCRATCH_CLEAN = 1  # include/pxsom.h PXSOM_TABLES_SCRATCH_CLEAN
 
 
+def _with_scratch_flag(workspace: AssignSumsWorkspace, n: int, what: str, call) -> None:
+    """``call(flags)`` with PXSOM_TABLES_SCRATCH_CLEAN while the workspace vouches for a zero statistics region.  It is
+    vouched for again only after a call that ran over rows (which leaves the region zero) or cleared the region itself
+    (no flag); an empty call with the flag touches nothing, and the next call clears once more; a failed call drops the
+    promise."""
+    flags, workspace.clean = (TABLES_SCRATCH_CLEAN if workspace.clean else 0), False
+    _capi.check(call(flags), what)
+    workspace.clean = n > 0 or not flags
+
+
 def assign_sums(x: torch.Tensor, w: torch.Tensor, labels: Optional[torch.Tensor] = None,
                 sums: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
                 workspace: Optional[AssignSumsWorkspace] = None):
@@ -983,13 +977,9 @@ def assign_sums(x: torch.Tensor, w: torch.Tensor, labels: Optional[torch.Tensor]
         counts = torch.zeros(k, dtype=torch.int64, device=x.device)
     if workspace is None or not workspace.fits(n, c, k):
         workspace = AssignSumsWorkspace(n, c, k, x.device)
-    flags, workspace.clean = (TABLES_SCRATCH_CLEAN if workspace.clean else 0), False
-    rc = _capi.lib().pxsom_assign_sums_ex(x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, labels.data_ptr(), sums.data_ptr(),
-                                          counts.data_ptr(), workspace.buf.data_ptr(), workspace.bytes, flags, _capi.stream_ptr())
-    _capi.check(rc, "pxsom_assign_sums_ex")
-    # vouched for again only after a call that ran over rows (which leaves the region zero) or cleared the region itself (no
-    # flag); an empty call with the flag touches nothing, and the next call clears once more
-    workspace.clean = n > 0 or not flags
+    _with_scratch_flag(workspace, n, "pxsom_assign_sums_ex", lambda flags: _capi.lib().pxsom_assign_sums_ex(
+        x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, labels.data_ptr(), sums.data_ptr(), counts.data_ptr(),
+        workspace.buf.data_ptr(), workspace.bytes, flags, _capi.stream_ptr()))
     return labels, sums, counts
 
 
@@ -1002,12 +992,10 @@ def assign_means(x: torch.Tensor, w: torch.Tensor, labels: torch.Tensor, sums: t
     k = w.shape[0]
     if not workspace.fits(n, c, k):
         raise ValueError("workspace does not fit this matrix")
-    flags, workspace.clean = (TABLES_SCRATCH_CLEAN if workspace.clean else 0), False
-    rc = _capi.lib().pxsom_assign_means_ex(x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, labels.data_ptr(), sums.data_ptr(),
-                                           counts.data_ptr(), means.data_ptr() if means is not None else None,
-                                           workspace.buf.data_ptr(), workspace.bytes, flags, _capi.stream_ptr())
-    _capi.check(rc, "pxsom_assign_means_ex")
-    workspace.clean = n > 0 or not flags   # as assign_sums
+    _with_scratch_flag(workspace, n, "pxsom_assign_means_ex", lambda flags: _capi.lib().pxsom_assign_means_ex(
+        x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, labels.data_ptr(), sums.data_ptr(), counts.data_ptr(),
+        means.data_ptr() if means is not None else None, workspace.buf.data_ptr(), workspace.bytes, flags,
+        _capi.stream_ptr()))
 
 
 # pxsom_cellquant (K12): image dtypes (PXSOM_SEG_* codes) and modes
@@ -1160,14 +1148,10 @@ def neighbor_thresholds(distlim) -> Tuple[float, float]:
     return (0.0 if at_lim is None else as_double(at_lim)), as_double(above_zero - 1)
 
 
-def neighbor_counts(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_types: int, distlim,
-                    self_neighbor: bool = False) -> torch.Tensor:
-    """pxsom_neighbor_counts: ``counts[i, t]`` (``[n, n_types]`` int32, HBM) = how many cells j of cell i's FOV with
-    ``types[j] == t`` have ``float32(dist(i, j)) < distlim`` (and ``!= 0`` unless ``self_neighbor``), dist the binary64
-    Euclidean distance of the centroids ``xy`` [n, 2] -- the reference's compute_neighbor_counts over calc_dist_matrix's
-    matrix, which is never built.  ``types`` [n] int32 / int64 in [0, n_types); ``seg`` [F + 1] int64 offsets (FOV f is
-    rows seg[f] .. seg[f + 1], seg[0] = 0, seg[F] = n, empty FOVs allowed).  Rows come in and go out in the caller's
-    order: the sort by type inside each FOV that the kernel wants is done here."""
+def _cells_sorted_by_type(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_types: int):
+    """The arguments :func:`neighbor_counts` and :func:`nearest_type_means` share, checked (one read-back), and the cells
+    as their kernels want them: sorted by type inside each FOV.  Returns ``(xy_s, types_s, seg, order, n_fovs)``; sorted
+    row r is the caller's row ``order[r]``.  With no cells the first two and ``order`` are None."""
     if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float64 or not xy.is_cuda:
         raise ValueError("xy must be an [n, 2] float64 HBM tensor")
     n, dev = xy.shape[0], xy.device
@@ -1175,10 +1159,8 @@ def neighbor_counts(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_
         raise ValueError("types must be an [n] int32 / int64 HBM vector on xy's device")
     if seg.dim() != 1 or seg.numel() < 1 or seg.dtype != torch.int64 or seg.device != dev:
         raise ValueError("seg must be an [F + 1] int64 HBM vector on xy's device")
-    n_types = operator.index(n_types)
     if n_types < 1:
         raise ValueError("n_types must be at least 1")
-    s_lim, s_zero = neighbor_thresholds(distlim)
     seg = seg.contiguous()
     n_fovs = seg.numel() - 1
     ok = torch.stack([seg[0] == 0, seg[-1] == n, (seg[1:] >= seg[:-1]).all(),
@@ -1187,14 +1169,29 @@ def neighbor_counts(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_
         raise ValueError("seg must be non-decreasing offsets from 0 to n")
     if not bool(ok[3]):
         raise ValueError("types must lie in [0, n_types)")
-    counts = torch.empty((n, n_types), dtype=torch.int32, device=dev)
     if n == 0:
-        return counts
+        return None, None, seg, None, n_fovs
     rows = torch.arange(n, device=dev)
     fov = torch.searchsorted(seg[1:], rows, right=True)
     order = torch.argsort(fov * n_types + types.to(torch.int64), stable=True)
-    xy_s = xy[order].contiguous()
-    types_s = types[order].to(torch.int32).contiguous()
+    return xy[order].contiguous(), types[order].to(torch.int32).contiguous(), seg, order, n_fovs
+
+
+def neighbor_counts(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_types: int, distlim,
+                    self_neighbor: bool = False) -> torch.Tensor:
+    """pxsom_neighbor_counts: ``counts[i, t]`` (``[n, n_types]`` int32, HBM) = how many cells j of cell i's FOV with
+    ``types[j] == t`` have ``float32(dist(i, j)) < distlim`` (and ``!= 0`` unless ``self_neighbor``), dist the binary64
+    Euclidean distance of the centroids ``xy`` [n, 2] -- the reference's compute_neighbor_counts over calc_dist_matrix's
+    matrix, which is never built.  ``types`` [n] int32 / int64 in [0, n_types); ``seg`` [F + 1] int64 offsets (FOV f is
+    rows seg[f] .. seg[f + 1], seg[0] = 0, seg[F] = n, empty FOVs allowed).  Rows come in and go out in the caller's
+    order: the sort by type inside each FOV that the kernel wants is done here."""
+    n_types = operator.index(n_types)
+    xy_s, types_s, seg, order, n_fovs = _cells_sorted_by_type(xy, types, seg, n_types)
+    s_lim, s_zero = neighbor_thresholds(distlim)
+    n = xy.shape[0]
+    counts = torch.empty((n, n_types), dtype=torch.int32, device=xy.device)
+    if n == 0:
+        return counts
     sorted_counts = torch.empty_like(counts)
     rc = _capi.lib().pxsom_neighbor_counts(xy_s.data_ptr(), types_s.data_ptr(), seg.data_ptr(), n_fovs, n, n_types,
                                            s_lim, s_zero, 1 if self_neighbor else 0, sorted_counts.data_ptr(),
@@ -1223,37 +1220,17 @@ def nearest_type_means(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor,
     -- the reference's calculate_mean_distance_to_cell_type over calc_dist_matrix's matrix, which is never built, bit for
     bit (float32 sum in numpy's pairwise order).  Arguments as for :func:`neighbor_counts`; ``1 <= k <= 32``.  Rows come
     in and go out in the caller's order: the sort by type inside each FOV that the kernel wants is done here."""
-    if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float64 or not xy.is_cuda:
-        raise ValueError("xy must be an [n, 2] float64 HBM tensor")
-    n, dev = xy.shape[0], xy.device
-    if types.dim() != 1 or types.shape[0] != n or types.dtype not in (torch.int32, torch.int64) or types.device != dev:
-        raise ValueError("types must be an [n] int32 / int64 HBM vector on xy's device")
-    if seg.dim() != 1 or seg.numel() < 1 or seg.dtype != torch.int64 or seg.device != dev:
-        raise ValueError("seg must be an [F + 1] int64 HBM vector on xy's device")
-    n_types = operator.index(n_types)
-    if n_types < 1:
-        raise ValueError("n_types must be at least 1")
     k = operator.index(k)
     if not 1 <= k <= NEAREST_MAX_K:
         raise ValueError("k must lie in 1 .. %d (the device route keeps the k nearest in registers), got %d"
                          % (NEAREST_MAX_K, k))
+    n_types = operator.index(n_types)
+    xy_s, types_s, seg, order, n_fovs = _cells_sorted_by_type(xy, types, seg, n_types)
     s_zero = _nearest_s_zero()
-    seg = seg.contiguous()
-    n_fovs = seg.numel() - 1
-    ok = torch.stack([seg[0] == 0, seg[-1] == n, (seg[1:] >= seg[:-1]).all(),
-                      ((types >= 0) & (types < n_types)).all()]).cpu()
-    if not bool(ok[:3].all()):
-        raise ValueError("seg must be non-decreasing offsets from 0 to n")
-    if not bool(ok[3]):
-        raise ValueError("types must lie in [0, n_types)")
-    means = torch.empty((n, n_types), dtype=torch.float32, device=dev)
+    n = xy.shape[0]
+    means = torch.empty((n, n_types), dtype=torch.float32, device=xy.device)
     if n == 0:
         return means
-    rows = torch.arange(n, device=dev)
-    fov = torch.searchsorted(seg[1:], rows, right=True)
-    order = torch.argsort(fov * n_types + types.to(torch.int64), stable=True)
-    xy_s = xy[order].contiguous()
-    types_s = types[order].to(torch.int32).contiguous()
     sorted_means = torch.empty_like(means)
     rc = _capi.lib().pxsom_nearest_type_means(xy_s.data_ptr(), types_s.data_ptr(), seg.data_ptr(), n_fovs, n, n_types, k,
                                               s_zero, sorted_means.data_ptr(), _capi.stream_ptr())
