@@ -112,6 +112,10 @@ SYMBOLS = {
     "pxsom_cellquant": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i64, ctypes.c_int32,
                                ctypes.c_int32, _vp, _i64, ctypes.c_int32, ctypes.c_int32, _i32, _f64, _i32, _vp, _vp,
                                _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    "pxsom_region_shape_workspace_bytes": (_sz, [_i64, ctypes.c_int32, ctypes.c_int32, _i32]),
+    "pxsom_region_shape": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                                  _vp, _vp, _sz, _i32, _vp]),
+    "pxsom_region_hull": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp]),
     "pxsom_neighbor_counts": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _vp, _vp]),
     "pxsom_nearest_type_means": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f64, _vp, _vp]),
     "pxsom_silhouette": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -1,13 +1,19 @@
 """``ark.segmentation.marker_quantification.generate_cell_table`` (the reference's
-ark/segmentation/marker_quantification.py:455-593) under ``fast_extraction=True``: one row per cell with its size, its channel values
+ark/segmentation/marker_quantification.py:455-593): one row per cell with its size, its channel values
 (``total_intensity``, ``positive_pixel`` or ``center_weighting``), its label and centroid, optionally the same for the
 nucleus that overlaps it most, then the FOV and the mask type -- normalised by cell size, and arcsinh-transformed.
+With ``fast_extraction=False`` and at least one of ``regionprops_base``, ``regionprops_single_comp`` and
+``regionprops_multi_comp`` named, the morphology columns stand between the label and the FOV: area, eccentricity, the
+axis lengths, perimeter, convex_area, equivalent_diameter, the six derived ratios and ``nc_ratio``.
 
 The per-cell reduction of the ``[H, W, C]`` image is one pxsom_cellquant pass per (FOV, compartment) on the device
 (DESIGN.md K12): it returns counts, exact coordinate sums and the channel values in numpy's own summation order.  The
-two transforms (``size_norm``, ``arcsinh``) and the frame layout stay on the host in numpy.  The morphology regionprops
-of ``fast_extraction=False``, MIBItiff inputs and ``split_large_nuclei`` are not implemented (NotImplementedError);
-``create_marker_count_matrices`` / ``compute_marker_counts`` are not mirrored (they take and return xarray)."""
+two transforms (``size_norm``, ``arcsinh``) and the frame layout stay on the host in numpy.  The morphology comes from
+one pxsom_region_shape and one pxsom_region_hull pass per compartment: raw integers from the device,
+the float columns from regionprops_extraction on the host; skimage is taken by its documented algorithms and parity
+with skimage itself is not pinned.  The bare call (``fast_extraction=False`` with none of the three lists named) keeps
+raising NotImplementedError, as do MIBItiff inputs, ``split_large_nuclei`` and a base property outside the eight built
+ones; ``create_marker_count_matrices`` / ``compute_marker_counts`` are not mirrored (they take and return xarray)."""
 import concurrent.futures
 import warnings
 
@@ -17,6 +23,7 @@ import pandas as pd
 from .. import distributed, image_io
 from ..host_utils import list_folders, remove_file_extensions, verify_in_list
 from ..utils import data_utils
+from . import regionprops_extraction as rpe
 
 EXTRACTION_OPTIONS = ["positive_pixel", "center_weighting", "total_intensity"]   # signal_extraction.EXTRACTION_FUNCTION
 PRE_CHANNEL_COL, POST_CHANNEL_COL = "cell_size", "label"                          # ark.settings
@@ -43,7 +50,8 @@ def _upload_image(image):
 
 def _quantify(image_dev, seg, mode, threshold, nuc=None) -> dict:
     """pxsom_cellquant over one compartment: host label images in, host tables out -- ``keys`` (the labels), ``count``,
-    ``sums`` [n, 2], ``values`` [n, C] and, with ``nuc``, ``nuc_keys`` and ``nuc`` (index into ``nuc_keys``, -1: none)."""
+    ``sums`` [n, 2], ``bbox`` [n, 4], ``values`` [n, C] and, with ``nuc``, ``nuc_keys`` and ``nuc`` (index into
+    ``nuc_keys``, -1: none).  ``_device`` keeps the uploaded label image and the device tables for :func:`_region_raw`."""
     import torch
     from .. import som_device
     dev = image_dev.device
@@ -51,9 +59,31 @@ def _quantify(image_dev, seg, mode, threshold, nuc=None) -> dict:
     def up(a):
         a = np.ascontiguousarray(a)
         return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
-    got = som_device.cell_quantify(up(seg), image_dev, mode=mode, threshold=threshold,
+    seg_dev = up(seg)
+    got = som_device.cell_quantify(seg_dev, image_dev, mode=mode, threshold=threshold,
                                    nuc=up(nuc) if nuc is not None else None)
-    return {k: v.cpu().numpy() for k, v in got.items()}
+    out = {k: v.cpu().numpy() for k, v in got.items()}
+    out["_device"] = dict(seg=seg_dev, keys=got["keys"], count=got["count"], sums=got["sums"], bbox=got["bbox"])
+    return out
+
+
+def _region_raw(seg, q=None, **thresholds) -> dict:
+    """pxsom_region_shape and pxsom_region_hull over one compartment: a host label image in, the raw integers of
+    som_device.region_props out as host arrays, the cells the device leaves out filled by the host route.  With the
+    result ``q`` of :func:`_quantify` over the same label image, its uploaded image, key table, counts, sums and boxes
+    are reused: no second upload, no second key table, and the shape pass skips the statistics atomics."""
+    import torch
+    from .. import _capi, som_device
+    kept = q.get("_device") if q is not None else None
+    if kept is not None:
+        got = som_device.region_props(kept["seg"], keys=kept["keys"], count=kept["count"], sums=kept["sums"],
+                                      bbox=kept["bbox"], **thresholds)
+    else:
+        dev = _capi.require_gpu()
+        a = np.ascontiguousarray(seg)
+        got = som_device.region_props(torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev), **thresholds)
+    raw = {k: v.cpu().numpy() for k, v in got.items()}
+    return rpe.fill_left_out(raw, seg, **thresholds)
 
 
 # ---- host side ----------------------------------------------------------------------------------------------------
@@ -73,16 +103,20 @@ def _as_label_plane(seg, what) -> np.ndarray:
     return seg
 
 
-def _raw_rows(q, n_channels):
-    """(cell_size, channels, label, centroid-0, centroid-1) of a quantify result as a float64 [n, C + 4] block."""
+def _raw_rows(q, n_channels, morph=None):
+    """(cell_size, channels, label, then centroid-0, centroid-1 or the morphology block ``morph``) of a quantify result
+    as a float64 [n, C + 2 + ...] block."""
     keys = np.asarray(q["keys"], dtype=np.int64)
     count = np.asarray(q["count"], dtype=np.int64)
     sums = np.asarray(q["sums"], dtype=np.int64).reshape(-1, 2)
-    out = np.zeros((keys.size, n_channels + 4), dtype=np.float64)
+    tail = 2 if morph is None else morph.shape[1]
+    out = np.zeros((keys.size, n_channels + 2 + tail), dtype=np.float64)
     out[:, 0] = count
     out[:, 1:1 + n_channels] = np.asarray(q["values"], dtype=np.float64).reshape(-1, n_channels)
     out[:, 1 + n_channels] = keys
-    if keys.size:
+    if morph is not None:
+        out[:, 2 + n_channels:] = morph
+    elif keys.size:
         out[:, 2 + n_channels] = sums[:, 0] / count     # coords.mean(axis=0): exact integer sums, one division
         out[:, 3 + n_channels] = sums[:, 1] / count
     return out
@@ -91,7 +125,7 @@ def _raw_rows(q, n_channels):
 def _transforms(raw, n_channels):
     """(size_norm, arcsinh of size_norm) of one compartment's raw block (transform_expression_matrix): channels divided
     by cell_size where it is > 0 -- 0 where it is not (the reference leaves those entries uninitialised) -- then
-    arcsinh(x * 100)."""
+    arcsinh(x * 100).  The other columns, the morphology among them, pass through."""
     ch = slice(1, 1 + n_channels)
     norm = raw.copy()
     size = raw[:, :1]
@@ -101,12 +135,39 @@ def _transforms(raw, n_channels):
     return norm, asinh
 
 
-def _fov_frames(fov, image_dev, channels, segs, mask_types, add_underscore, nuclear_counts, mode, threshold):
+def _morph_block(seg, q, props):
+    """The morphology columns of one compartment as a float64 [n, len(names)] block in the table's order
+    (regionprops_extraction.table_names), rows in the order of the quantify result ``q``."""
+    base, single, _, thresholds = props
+    raw = _region_raw(seg, q, **thresholds)
+    if not np.array_equal(np.asarray(raw["keys"], dtype=np.int64), np.asarray(q["keys"], dtype=np.int64)):
+        raise RuntimeError("generate_cell_table: the morphology pass and the signal pass name different cells")
+    cols = rpe.morphology(raw)
+    names = rpe.table_names(base, single)
+    block = np.zeros((np.asarray(raw["keys"]).size, len(names)), dtype=np.float64)
+    for j, name in enumerate(names):
+        block[:, j] = cols[name]
+    return block
+
+
+def get_single_compartment_props(segmentation_labels, regionprops_base, regionprops_single_comp, **kwargs):
+    """The reference's get_single_compartment_props without ``coords``: one row per cell of a ``[H, W]`` label image,
+    labels ascending -- the base properties in list order (``centroid`` as ``centroid-0``, ``centroid-1`` in its place),
+    then the single-compartment ones; ``kwargs`` may set num_concavities' three thresholds.  An all-background image
+    gives an empty frame with the same columns."""
+    base, single, _ = rpe.resolve_lists(regionprops_base, regionprops_single_comp, [])
+    seg = _as_label_plane(segmentation_labels, "segmentation_labels")
+    return rpe.props_frame(_region_raw(seg, **rpe.concavity_thresholds(**kwargs)), base, single)
+
+
+def _fov_frames(fov, image_dev, channels, segs, mask_types, add_underscore, nuclear_counts, mode, threshold,
+                props=None):
     """The (size-normalised, arcsinh) frames of one FOV, one pair per mask type, from its segmentations ``segs``
-    (mask file suffix -> label plane)."""
-    names = [PRE_CHANNEL_COL] + list(channels) + BASE_NAMES
+    (mask file suffix -> label plane).  ``props`` (base, single, multi, thresholds) adds the morphology columns."""
+    tail = BASE_NAMES[1:] if props is None else rpe.table_names(props[0], props[1])
     frames = []
     for mask_type in mask_types:
+        names = [PRE_CHANNEL_COL] + list(channels) + [POST_CHANNEL_COL] + tail
         mask_type, mask_suff = _mask_name(mask_type, add_underscore)
         compartments = ["whole_cell"]
         if nuclear_counts and mask_type == "whole_cell":
@@ -118,20 +179,33 @@ def _fov_frames(fov, image_dev, channels, segs, mask_types, add_underscore, nucl
         q = _quantify(image_dev, seg, mode, threshold, nuc=nuc)
         if np.asarray(q["keys"]).size == 0:
             warnings.warn("No cells found in the following image: {}".format(fov))
-        raw = _raw_rows(q, len(channels))
+        raw = _raw_rows(q, len(channels), None if props is None else _morph_block(seg, q, props))
+        rows = None
+        if nuclear_counts:
+            qn = _quantify(image_dev, nuc, mode, threshold)
+            if np.asarray(qn["keys"]).size == 0:
+                warnings.warn("No nuclei found in the following image: {}".format(fov))
+            nuc_raw = _raw_rows(qn, len(channels), None if props is None else _morph_block(nuc, qn, props))
+            which = np.asarray(q["nuc"], dtype=np.int64)
+            rows = np.zeros_like(raw)
+            rows[which >= 0] = nuc_raw[which[which >= 0]]
+            # nc_ratio: appended to both compartments once a cell of the FOV has a nucleus (the reference adds the
+            # feature inside its loop over the cells, so a FOV without any never gets the column)
+            if props is not None and "nc_ratio" in props[2] and (which >= 0).any():
+                if "area" not in names:
+                    raise ValueError("generate_cell_table: nc_ratio needs 'area' in regionprops_base")
+                at = names.index("area")
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    ratio = np.nan_to_num(rows[:, at] / raw[:, at], posinf=0, neginf=0)
+                raw = np.concatenate((raw, ratio[:, None]), axis=1)
+                rows = np.concatenate((rows, ratio[:, None]), axis=1)
+                names = names + ["nc_ratio"]
         norm, asinh = _transforms(raw, len(channels))
         norm_df = pd.DataFrame(data=norm, columns=names)
         asinh_df = pd.DataFrame(data=asinh, columns=names)
         norm_df[POST_CHANNEL_COL] = norm_df[POST_CHANNEL_COL].astype(np.int32)
         asinh_df[POST_CHANNEL_COL] = asinh_df[POST_CHANNEL_COL].astype(np.int32)
         if nuclear_counts:
-            qn = _quantify(image_dev, nuc, mode, threshold)
-            if np.asarray(qn["keys"]).size == 0:
-                warnings.warn("No nuclei found in the following image: {}".format(fov))
-            nuc_raw = _raw_rows(qn, len(channels))
-            which = np.asarray(q["nuc"], dtype=np.int64)
-            rows = np.zeros_like(raw)
-            rows[which >= 0] = nuc_raw[which[which >= 0]]
             nuc_norm, nuc_asinh = _transforms(rows, len(channels))
             nuc_names = [f + "_nuclear" for f in names]
             norm_df = pd.concat((norm_df, pd.DataFrame(data=nuc_norm, columns=nuc_names)), axis=1)
@@ -166,11 +240,18 @@ def _read_fov(segmentation_dir, tiff_dir, img_sub_folder, fov, suffixes):
 def generate_cell_table(segmentation_dir, tiff_dir, img_sub_folder="TIFs", is_mibitiff=False, fovs=None,
                         extraction='total_intensity', nuclear_counts=False, fast_extraction=False,
                         mask_types=['whole_cell'], add_underscore=True, **kwargs):
-    """The reference's generate_cell_table under ``fast_extraction=True``: ``(cell_table_size_normalized,
-    cell_table_arcsinh_transformed)``, FOVs sorted, cells in ascending label order, each FOV's frame with its own
-    RangeIndex.  ``signal_kwargs={'threshold': t}`` sets positive_pixel's threshold (default 0).  A cell without a
-    nucleus keeps a zero ``_nuclear`` row.  Under a process group the FOVs are sharded over the ranks and every rank
-    returns the whole table."""
+    """The reference's generate_cell_table: ``(cell_table_size_normalized, cell_table_arcsinh_transformed)``, FOVs
+    sorted, cells in ascending label order, each FOV's frame with its own RangeIndex.  ``signal_kwargs={'threshold': t}``
+    sets positive_pixel's threshold (default 0).  A cell without a nucleus keeps a zero ``_nuclear`` row.
+
+    ``fast_extraction=False`` runs once at least one of ``regionprops_base``, ``regionprops_single_comp`` and
+    ``regionprops_multi_comp`` is named (a list not named takes the reference's default); the bare call raises
+    NotImplementedError.  The columns are then ``cell_size``, the channels, ``label``, the base properties in list order
+    with ``centroid-0``, ``centroid-1`` at the end of the base block, the single-compartment properties and, with
+    ``nuclear_counts`` in a FOV where some cell has a nucleus, ``nc_ratio``.  ``regionprops_kwargs`` may set
+    ``small_concavity_minimum``, ``max_compactness`` and ``large_concavity_minimum``.  With ``fast_extraction=True`` the
+    lists are ignored.  Under a process group the FOVs are sharded over the ranks and every rank returns the whole
+    table."""
     if is_mibitiff:
         raise NotImplementedError("generate_cell_table: MIBItiff inputs are not implemented; "
                                   "use single-channel TIFFs (is_mibitiff=False)")
@@ -178,10 +259,14 @@ def generate_cell_table(segmentation_dir, tiff_dir, img_sub_folder="TIFs", is_mi
         fovs = list_folders(tiff_dir)
     fovs = remove_file_extensions(fovs)
     verify_in_list(extraction=extraction, extraction_options=EXTRACTION_OPTIONS)
+    props = None
     if not fast_extraction:
-        raise NotImplementedError("generate_cell_table: the morphology regionprops of fast_extraction=False (area, "
-                                  "perimeter, convex area, concavities, nc_ratio, ...) are not implemented; "
-                                  "fast_extraction=True is what runs")
+        lists = [kwargs.get(k) for k in ("regionprops_base", "regionprops_single_comp", "regionprops_multi_comp")]
+        if all(v is None for v in lists):
+            raise NotImplementedError("generate_cell_table: the morphology regionprops of fast_extraction=False (area, "
+                                      "perimeter, convex area, concavities, nc_ratio, ...) are not implemented; "
+                                      "fast_extraction=True is what runs")
+        props = rpe.resolve_lists(*lists) + (rpe.concavity_thresholds(**kwargs.get("regionprops_kwargs", {})),)
     if kwargs.get("split_large_nuclei", False):
         raise NotImplementedError("generate_cell_table: split_large_nuclei=True is not implemented")
     threshold = kwargs.get("signal_kwargs", {}).get("threshold", 0)
@@ -202,7 +287,7 @@ def generate_cell_table(segmentation_dir, tiff_dir, img_sub_folder="TIFs", is_mi
                 image_dev = _upload_image(image)
                 thr = _threshold_for(image.dtype, threshold)
                 done[fov] = _fov_frames(fov, image_dev, channels, segs, mask_types, add_underscore, nuclear_counts,
-                                        extraction, thr)
+                                        extraction, thr, props)
     except Exception as e:      # noqa: BLE001 -- travels to every rank below, re-raised there
         error = e
     gathered = distributed.allgather_objects((error, done))

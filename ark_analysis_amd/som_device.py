@@ -1110,6 +1110,70 @@ def cell_quantify(seg: torch.Tensor, img: torch.Tensor, keys: Optional[torch.Ten
     return out
 
 
+# pxsom_region_shape / pxsom_region_hull (K17)
+REGION_FORCE_SEARCH = 1
+REGION_MAX_SIDE = 64           # the device route of the hull: bounding boxes up to 64 x 64
+CONCAVITY_DEFAULTS = {"small_concavity_minimum": 10, "max_compactness": 60, "large_concavity_minimum": 150}
+
+
+def region_props(seg: torch.Tensor, keys: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                 sums: Optional[torch.Tensor] = None, bbox: Optional[torch.Tensor] = None,
+                 small_concavity_minimum: float = 10, max_compactness: float = 60,
+                 large_concavity_minimum: float = 150, force_search: bool = False) -> dict:
+    """The raw integers of the morphology regionprops of a ``[H, W]`` HBM label image (any row stride), one row per key
+    (default :func:`label_keys` of ``seg``): a dict of HBM tensors ``keys``, ``count`` [n] int64, ``sums`` [n, 2] int64,
+    ``bbox`` [n, 4] int32 (taken from the arguments when :func:`cell_quantify` already produced all three, computed in
+    the same pass otherwise), ``shape`` [n, 6] int64 (sum r^2, sum c^2, sum r c, and the border pixels of perimeter
+    weight 1, sqrt 2 and (1 + sqrt 2) / 2), ``hull`` [n, 4] int64 (convex area, convex row sum, convex column sum,
+    concavities) and ``left_out`` [n] int32: 1 for a cell whose bounding box is past 64 x 64, whose ``hull`` row is 0 and
+    is the host route's to fill (regionprops_extraction.host_hull)."""
+    h, w, ld = _label_image(seg, "seg")
+    if keys is None:
+        keys = label_keys(seg)
+    kmin, kmax = _key_range(keys)
+    n = keys.numel()
+    if n and kmin <= 0:
+        raise ValueError("keys must be positive")
+    given = [t is not None for t in (count, sums, bbox)]
+    if any(given) and not all(given):
+        raise ValueError("count, sums and bbox go together (all three from cell_quantify, or none)")
+    dev = seg.device
+    have = all(given)
+    if have:
+        ok = (count.dtype == torch.int64 and tuple(count.shape) == (n,) and sums.dtype == torch.int64 and
+              tuple(sums.shape) == (n, 2) and bbox.dtype == torch.int32 and tuple(bbox.shape) == (n, 4))
+        if not ok or not all(t.is_cuda and t.is_contiguous() for t in (count, sums, bbox)):
+            raise ValueError("count [n] int64, sums [n, 2] int64 and bbox [n, 4] int32 must be contiguous HBM tensors")
+    else:
+        count = torch.empty(n, dtype=torch.int64, device=dev)
+        sums = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    for name, v in (("small_concavity_minimum", small_concavity_minimum), ("max_compactness", max_compactness),
+                    ("large_concavity_minimum", large_concavity_minimum)):
+        if float(v) != float(v):
+            raise ValueError("%s must not be NaN" % name)
+    out = {"keys": keys, "count": count, "sums": sums, "bbox": bbox,
+           "shape": torch.empty((n, 6), dtype=torch.int64, device=dev),
+           "hull": torch.empty((n, 4), dtype=torch.int64, device=dev),
+           "left_out": torch.empty(n, dtype=torch.int32, device=dev)}
+    flags = REGION_FORCE_SEARCH if force_search else 0
+    lib = _capi.lib()
+    wsb = lib.pxsom_region_shape_workspace_bytes(n, kmin, kmax, flags)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    code = SEG_DTYPES[seg.dtype]
+    rc = lib.pxsom_region_shape(seg.data_ptr(), code, ld, h, w, keys.data_ptr() if n else None, n, kmin, kmax,
+                                out["shape"].data_ptr(), None if have else count.data_ptr(),
+                                None if have else sums.data_ptr(), None if have else bbox.data_ptr(), ws.data_ptr(),
+                                wsb, flags, _capi.stream_ptr())
+    _capi.check(rc, "pxsom_region_shape")
+    rc = lib.pxsom_region_hull(seg.data_ptr(), code, ld, h, w, keys.data_ptr() if n else None, n, count.data_ptr(),
+                               bbox.data_ptr(), float(small_concavity_minimum), float(max_compactness),
+                               float(large_concavity_minimum), out["hull"].data_ptr(), out["left_out"].data_ptr(),
+                               _capi.stream_ptr())
+    _capi.check(rc, "pxsom_region_hull")
+    return out
+
+
 # ---- neighbourhood matrix (K13) -------------------------------------------------------------------------------------
 def _smallest_double(pred):
     """The smallest double s in [0, +inf] with ``pred(s)`` for a monotone pred (False, ..., False, True, ..., True),

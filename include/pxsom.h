@@ -580,6 +580,44 @@ int pxsom_cellquant(const void *seg_dev, int seg_dtype, int64_t ld, const void *
                     int64_t *count_dev, int64_t *sums_dev, int32_t *bbox_dev, double *values_dev, int32_t *nuc_out_dev,
                     void *workspace_dev, size_t workspace_bytes, int flags, void *stream);
 
+/* ---- cell morphology: the raw integers of the regionprops columns of generate_cell_table (K17) ------------------------
+ * reference: ark/segmentation/marker_quantification.py get_single_compartment_props (skimage regionprops area,
+ * eccentricity, axis lengths, perimeter, convex_area) and ark/segmentation/regionprops_extraction.py (centroid_dif,
+ * num_concavities), by their documented algorithms in integer geometry; parity with skimage itself is not pinned.
+ * Symbols added under ABI 9, none changed.  seg_dev, keys_dev and the cells: as for pxsom_cellquant; a label past int32
+ * is background.
+ *
+ * pxsom_region_shape: per cell i, shape_dev[6i .. 6i + 5] (int64, every entry written) =
+ *   sum r^2, sum c^2, sum r c over the cell's pixels (image coordinates), then the number of border pixels in each weight
+ *   class of skimage.measure.perimeter(neighbourhood=4): a border pixel has a 4-neighbour that is not the cell or lies
+ *   outside the image, its code is 1 + 2 * (4-neighbours that are border pixels of the cell) + 10 * (diagonal ones);
+ *   codes 5, 7, 15, 17, 25, 27 weigh 1, codes 21, 33 weigh sqrt 2, codes 13, 23 weigh (1 + sqrt 2) / 2.
+ * count_dev, sums_dev, bbox_dev: all NULL, or all given and then written as pxsom_cellquant writes them.  Integer atomics
+ * only: the same input gives the same bits.  Workspace: pxsom_region_shape_workspace_bytes (the dense LUT of the K10 rule,
+ * 0 under PXSOM_REGION_FORCE_SEARCH; both routes give identical results).
+ *
+ * pxsom_region_hull: per cell i whose bounding box (bbox_dev, count_dev as pxsom_cellquant or pxsom_region_shape wrote
+ * them) is at most 64 x 64, hull_dev[4i .. 4i + 3] (int64) =
+ *   the pixels of the convex image -- centres inside or ON the hull of the diamond points (r +- 1/2, c), (r, c +- 1/2) of
+ *   the cell's pixels, decided in doubled integer coordinates -- their row sum and column sum, and the number of
+ *   concavities: 4-connected components of (convex image minus cell) with area a and perimeter p (the rule above on the
+ *   component alone, p = (n1 + n2 * sqrt 2) + n3 * ((1 + sqrt 2) / 2) in binary64 without contraction) for which
+ *   (a > small_concavity_minimum and p * p / a < max_compactness) or a > large_concavity_minimum.
+ * left_out_dev[i] (int32) = 1 for a cell with a larger box: its hull_dev entries are 0 and the caller computes them
+ * elsewhere.  An absent key (count 0) gives zeros.  A box outside the image is treated as an absent key, never read.
+ * The box is expected tight; in a box that is not, the pixels of the key inside it are the cell (none: zeros).
+ * Bad dtype codes, sizes, flags, NaN thresholds, pointers or workspace: PXSOM_ERR_INVALID_ARG before any HIP call. */
+#define PXSOM_REGION_FORCE_SEARCH 1
+size_t pxsom_region_shape_workspace_bytes(int64_t n_keys, int32_t key_min, int32_t key_max, int flags);
+int pxsom_region_shape(const void *seg_dev, int seg_dtype, int64_t ld, int h, int w, const int32_t *keys_dev,
+                       int64_t n_keys, int32_t key_min, int32_t key_max, int64_t *shape_dev, int64_t *count_dev,
+                       int64_t *sums_dev, int32_t *bbox_dev, void *workspace_dev, size_t workspace_bytes, int flags,
+                       void *stream);
+int pxsom_region_hull(const void *seg_dev, int seg_dtype, int64_t ld, int h, int w, const int32_t *keys_dev,
+                      int64_t n_keys, const int64_t *count_dev, const int32_t *bbox_dev, double small_concavity_minimum,
+                      double max_compactness, double large_concavity_minimum, int64_t *hull_dev, int32_t *left_out_dev,
+                      void *stream);
+
 /* ---- neighbourhood matrix: per-cell neighbour counts by phenotype, from the centroids (K13) -------------------------
  * reference: ark/analysis/spatial_analysis_utils.py calc_dist_matrix (cdist(...).astype(float32), one N x N matrix per
  * FOV) and compute_neighbor_counts (dist < distlim, dist == 0 removed unless self_neighbor, one-hot dot).  One
