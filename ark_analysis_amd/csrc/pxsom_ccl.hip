@@ -4,6 +4,8 @@
 //                                   with the component count and the area table
 //   pxsom_components_select         remove_small_holes' fill / the area filter of _create_object_mask, from the area table
 //   pxsom_binarize_plane            the three foreground predicates of _create_object_mask
+//   pxsom_label_regions             skimage.measure.label(img, background=0) of an integer label plane (K18): regions of
+//                                   equal non-zero value; stages 1 and 2 in valued forms, stages 3 and 4 as they are
 // (The blur of _create_object_mask is pxsom_gaussian_blur_plane_mode of pxsom_pre.hip.)
 //
 // Labelling is union-find on linear pixel indices, parent <= child everywhere, so the root of a component IS its first pixel
@@ -143,6 +145,106 @@ __global__ __launch_bounds__(256) void border_merge_kernel(int *__restrict__ par
         const int q = p - w;
         if (here && !left && ld_relaxed(parent + q - 1) >= 0) uf_union(parent, p, q - 1);
         if (left && !here && ld_relaxed(parent + q) >= 0) uf_union(parent, p - 1, q);
+    }
+}
+
+// ---- regions of equal value (K18): stages 1 and 2 where every join also tests value(p) == value(q) ---------------------
+// The shortcuts of the binary kernels hold once "foreground" reads "has this pixel's value": two horizontal neighbours
+// of one value are one run, so what a same-valued left neighbour also touches in the row above is left to it.
+template <typename T>
+__global__ __launch_bounds__(256) void tile_label_valued_kernel(const T *__restrict__ src, int64_t ld, int h, int w, int conn8,
+                                                                int *__restrict__ parent, int tiles_x, int64_t ntiles)
+{
+    __shared__ int lab[kTile * kTile];
+    __shared__ T val[kTile * kTile];
+    const int64_t tile = xcd_contiguous(blockIdx.x, ntiles);
+    if (tile >= ntiles) return;
+    const int ty0 = (int)(tile / tiles_x) * kTile, tx0 = (int)(tile % tiles_x) * kTile;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = tx0 + lane;
+
+    // run starts: a non-zero lane whose left neighbour holds another value; a lane's run begins at the highest start
+    // at or below it
+    for (int r = wave; r < kTile; r += 4) {
+        const int y = ty0 + r;
+        T v = 0;
+        if (y < h && x < w) v = src[(int64_t)y * ld + x];
+        val[r * kTile + lane] = v;
+        const long long wide = (long long)v;               // (every label dtype widens without two values meeting)
+        const long long left = __shfl_up(wide, 1);
+        const bool fg = v != 0;
+        const unsigned long long starts = __ballot(fg && (lane == 0 || left != wide));
+        const unsigned long long upto = starts & (lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull);
+        lab[r * kTile + lane] = fg ? r * kTile + 63 - __builtin_clzll(upto | 1ull) : -1;   // (a foreground lane: upto != 0)
+    }
+    __syncthreads();
+
+    for (int r = wave; r < kTile; r += 4) {
+        if (r == 0) continue;
+        const int p = r * kTile + lane, q = p - kTile;
+        const T v = val[p];
+        if (v == 0) continue;
+        const bool u = val[q] == v;
+        const bool ul = lane > 0 && val[q - 1] == v;
+        const bool ur = lane < 63 && val[q + 1] == v;
+        const bool left = lane > 0 && val[p - 1] == v;
+        if (conn8) {
+            if (u) {
+                if (!left) uf_union(lab, p, q);
+            } else {
+                if (ul && !left) uf_union(lab, p, q - 1);
+                if (ur) uf_union(lab, p, q + 1);
+            }
+        } else if (u && !(left && ul)) {
+            uf_union(lab, p, q);
+        }
+    }
+    __syncthreads();
+
+    for (int r = wave; r < kTile; r += 4) {
+        const int y = ty0 + r;
+        if (y >= h || x >= w) continue;
+        const int p = r * kTile + lane;
+        int root = -1;
+        if (lab[p] >= 0) {
+            const int lr = uf_find(lab, p);
+            root = (ty0 + lr / kTile) * w + tx0 + lr % kTile;
+        }
+        parent[(int64_t)y * w + x] = root;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void border_merge_valued_kernel(const T *__restrict__ src, int64_t ld, int *__restrict__ parent,
+                                                                  int h, int w, int conn8, int64_t n_rows, int64_t total)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    if (i < n_rows) {   // first row of a tile below the top
+        const int y = (int)(i / w + 1) * kTile, x = (int)(i % w);
+        const int p = y * w + x, q = p - w;
+        const T *row = src + (int64_t)y * ld, *above = row - ld;
+        const T v = row[x];
+        if (v == 0) return;
+        if (above[x] == v) {
+            uf_union(parent, p, q);      // an up-left or up-right of this value is in `up`'s run
+        } else if (conn8) {
+            if (x > 0 && above[x - 1] == v) uf_union(parent, p, q - 1);
+            if (x < w - 1 && above[x + 1] == v) uf_union(parent, p, q + 1);
+        }
+        return;
+    }
+    // first column of a tile right of the left edge
+    const int64_t j = i - n_rows;
+    const int x = (int)(j / h + 1) * kTile, y = (int)(j % h);
+    const int p = y * w + x;
+    const T *row = src + (int64_t)y * ld;
+    const T here = row[x], left = row[x - 1];
+    if (here != 0 && here == left) uf_union(parent, p, p - 1);
+    if (conn8 && y > 0 && y % kTile != 0 && here != left) {      // (equal: each reaches the other's diagonal through it)
+        const T *above = row - ld;
+        if (here != 0 && above[x - 1] == here) uf_union(parent, p, p - w - 1);
+        if (left != 0 && above[x] == left) uf_union(parent, p - 1, p - w);
     }
 }
 
@@ -366,6 +468,59 @@ PXSOM_EXPORT int pxsom_label_components(const uint8_t *fg_dev, int h, int w, int
     hipLaunchKernelGGL(finish_labels_kernel, dim3((unsigned)(((int64_t)total + kFinishSpan - 1) / kFinishSpan)), dim3(kChunk), 0, st, parent, total, w, labels_dev, ldo,
                        areas_dev, capacity);
     PXSOM_LAUNCH_CHECK("pxsom_label_components kernels");
+    return PXSOM_OK;
+}
+
+PXSOM_EXPORT size_t pxsom_label_regions_workspace_bytes(int h, int w) { return pxsom_label_components_workspace_bytes(h, w); }
+
+PXSOM_EXPORT int pxsom_label_regions(const void *seg_dev, int dtype, int h, int w, int64_t ld, int connectivity,
+                                     int32_t *labels_dev, int64_t ldo, int32_t *n_dev, int32_t *areas_dev, int64_t capacity,
+                                     void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    if (h < 1 || w < 1 || ld < w || ldo < w)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_label_regions: bad size or stride (h=%d w=%d ld=%lld ldo=%lld)", h, w,
+                           (long long)ld, (long long)ldo);
+    if (!pxsom::is_label_dtype(dtype))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_label_regions: dtype code %d is not a label dtype (%d .. %d)", dtype,
+                           PXSOM_SEG_U8, PXSOM_SEG_I64);
+    if (connectivity != 1 && connectivity != 2)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_label_regions: connectivity %d is not 1 or 2", connectivity);
+    if (capacity < 1)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_label_regions: capacity %lld is below 1", (long long)capacity);
+    if (!seg_dev || !labels_dev || !n_dev || !areas_dev || !workspace_dev)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_label_regions: null pointer");
+    if ((int64_t)h * w > INT32_MAX)
+        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_label_regions: %d x %d pixels are beyond int32", h, w);
+    if (workspace_bytes < pxsom_label_regions_workspace_bytes(h, w))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_label_regions: workspace of %zu bytes, %zu needed", workspace_bytes,
+                           pxsom_label_regions_workspace_bytes(h, w));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int total = h * w;
+    int *parent = static_cast<int *>(workspace_dev);
+    unsigned *counts = reinterpret_cast<unsigned *>(static_cast<char *>(workspace_dev) + pxsom::align_up((size_t)total * sizeof(int), 256));
+    const int64_t chunks = ccl_chunks(total);
+    const int tiles_x = (w + kTile - 1) / kTile, tiles_y = (h + kTile - 1) / kTile;
+    const int64_t ntiles = (int64_t)tiles_x * tiles_y;
+    const int conn8 = connectivity == 2 ? 1 : 0;
+    const int64_t n_rows = (int64_t)(tiles_y - 1) * w, n_cols = (int64_t)(tiles_x - 1) * h;
+
+    PXSOM_HIP_TRY(hipMemsetAsync(areas_dev, 0, (size_t)capacity * sizeof(int32_t), st));
+    pxsom::dispatch_label(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const T *src = static_cast<const T *>(seg_dev);
+        hipLaunchKernelGGL(tile_label_valued_kernel<T>, dim3((unsigned)((ntiles + 7) / 8 * 8)), dim3(256), 0, st, src, ld, h, w,
+                           conn8, parent, tiles_x, ntiles);
+        if (n_rows + n_cols > 0)
+            hipLaunchKernelGGL(border_merge_valued_kernel<T>, dim3((unsigned)((n_rows + n_cols + 255) / 256)), dim3(256), 0, st,
+                               src, ld, parent, h, w, conn8, n_rows, n_rows + n_cols);
+        return 0;
+    });
+    hipLaunchKernelGGL(flatten_count_kernel, dim3((unsigned)chunks), dim3(kChunk), 0, st, parent, total, counts);
+    hipLaunchKernelGGL(ccl_scan_kernel, dim3(1), dim3(1024), 0, st, counts, chunks, n_dev);
+    hipLaunchKernelGGL(rank_roots_kernel, dim3((unsigned)chunks), dim3(kChunk), 0, st, parent, total, w, counts, labels_dev, ldo);
+    hipLaunchKernelGGL(finish_labels_kernel, dim3((unsigned)(((int64_t)total + kFinishSpan - 1) / kFinishSpan)), dim3(kChunk), 0, st,
+                       parent, total, w, labels_dev, ldo, areas_dev, capacity);
+    PXSOM_LAUNCH_CHECK("pxsom_label_regions kernels");
     return PXSOM_OK;
 }
 

@@ -271,13 +271,13 @@ _SAMPLE_FORMATS = {"u": 1, "i": 2, "f": 3}
 
 
 def write_image(path, image: np.ndarray) -> None:
-    """A 2-D uint8 / uint16 / int16 / int32 / float32 array as a baseline TIFF in its own dtype: little-endian,
+    """A 2-D uint8 / uint16 / int16 / int32 / uint32 / float32 array as a baseline TIFF in its own dtype: little-endian,
     uncompressed, one strip, with the SampleFormat tag -- what the cluster masks are saved as (int16 stays int16,
-    which Pillow cannot write).  :func:`read_image` reads it back unchanged."""
+    which Pillow cannot write).  :func:`read_image` reads it back unchanged (a uint32 file: :func:`read_tiff_shaped`)."""
     import struct
     image = np.asarray(image)
-    if image.ndim != 2 or image.dtype.name not in ("uint8", "uint16", "int16", "int32", "float32"):
-        raise ValueError("write_image takes a 2-D uint8, uint16, int16, int32 or float32 array, got %s %s"
+    if image.ndim != 2 or image.dtype.name not in ("uint8", "uint16", "int16", "int32", "uint32", "float32"):
+        raise ValueError("write_image takes a 2-D uint8, uint16, int16, int32, uint32 or float32 array, got %s %s"
                          % (image.dtype, image.shape))
     data = np.ascontiguousarray(image, dtype=image.dtype.newbyteorder("<"))
     if data.nbytes >= 1 << 32:

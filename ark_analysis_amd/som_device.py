@@ -915,6 +915,179 @@ def object_mask(img: torch.Tensor, sigma, thresh, hole_size, min_area, max_area,
     return components_select(labels, areas, "keep", min_area=min_area, max_area=max_area, out=labels)
 
 
+# ---- merging object masks into the cell segmentation (K18) --------------------------------------------------------------
+PAIR_CAPACITY_MAX = 1 << 27                          # kMaxPairCapacity of csrc/pxsom_merge.hip
+
+
+def label_regions(seg: torch.Tensor, connectivity: int, out: Optional[torch.Tensor] = None,
+                  capacity: Optional[int] = None):
+    """``skimage.measure.label(seg, background=0, connectivity=connectivity)`` of a ``[H, W]`` integer HBM label plane
+    (uint8 .. int64, rows contiguous, any row stride): regions of equal non-zero value, touching regions of different
+    values kept apart.  Returns ``(labels, n, areas)`` with the conventions of :func:`label_components`; the default
+    capacity is every image's worst case, ``H W + 1``."""
+    h, w, ld = _label_image(seg, "seg")
+    if connectivity not in (1, 2):
+        raise ValueError("connectivity must be 1 or 2, got %r" % (connectivity,))
+    labels = _label_plane(out, h, w, seg.device, "out")
+    capacity = h * w + 1 if capacity is None else int(capacity)
+    n = torch.empty(1, dtype=torch.int32, device=seg.device)
+    areas = torch.empty(max(capacity, 0), dtype=torch.int32, device=seg.device)
+    lib = _capi.lib()
+    wsb = lib.pxsom_label_regions_workspace_bytes(h, w)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=seg.device)
+    rc = lib.pxsom_label_regions(seg.data_ptr(), SEG_DTYPES[seg.dtype], h, w, ld, int(connectivity), labels.data_ptr(),
+                                 _ld(labels), n.data_ptr(), areas.data_ptr(), capacity, ws.data_ptr(), wsb,
+                                 _capi.stream_ptr())
+    _capi.check(rc, "pxsom_label_regions")
+    return labels, n, areas
+
+
+def _label_pair(a: torch.Tensor, b: torch.Tensor):
+    for name, t in (("a", a), ("b", b)):
+        if t.dim() != 2 or not t.is_cuda or t.dtype != torch.int32 or t.shape[0] == 0 or t.shape[1] == 0 or \
+                (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError("%s must be a non-empty [H, W] int32 HBM plane with contiguous rows" % name)
+    if a.shape != b.shape:
+        raise ValueError("a and b must have one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    return a.shape
+
+
+def pair_overlaps(a: torch.Tensor, b: torch.Tensor, n_a: Optional[int] = None, n_b: Optional[int] = None) -> torch.Tensor:
+    """The label pairs two ``[H, W]`` int32 HBM planes share: ``[P, 3]`` int32 in HBM, one row ``(a, b, pixels)`` per
+    pair with ``1 <= a <= n_a``, ``1 <= b <= n_b`` (default: every positive label) and ``pixels > 0``, sorted by
+    ``(a, b)``.  Two calls of pxsom_pair_overlaps: the first counts the runs of the image, which is read back and sizes
+    the list and the table of the second."""
+    h, w = _label_pair(a, b)
+    top = 2 ** 31 - 1
+    n_a, n_b = (top if v is None else int(v) for v in (n_a, n_b))
+    if not (0 <= n_a <= top and 0 <= n_b <= top):
+        raise ValueError("n_a and n_b must lie in 0 .. 2147483647")
+    lib = _capi.lib()
+    n = torch.empty(2, dtype=torch.int32, device=a.device)
+
+    def call(pairs, capacity, ws, wsb):
+        rc = lib.pxsom_pair_overlaps(a.data_ptr(), _ld(a), b.data_ptr(), _ld(b), h, w, n_a, n_b, pairs, capacity,
+                                     n.data_ptr(), ws, wsb, _capi.stream_ptr())
+        _capi.check(rc, "pxsom_pair_overlaps")
+
+    call(None, 0, None, 0)
+    runs = int(n[1].item())
+    if runs == 0:
+        return torch.empty((0, 3), dtype=torch.int32, device=a.device)
+    if runs > PAIR_CAPACITY_MAX:
+        raise NotImplementedError("pair_overlaps: %d runs of label pairs are beyond the limit %d" % (runs, PAIR_CAPACITY_MAX))
+    pairs = torch.empty((runs, 3), dtype=torch.int32, device=a.device)
+    wsb = lib.pxsom_pair_overlaps_workspace_bytes(runs)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=a.device)
+    call(pairs.data_ptr(), runs, ws.data_ptr(), wsb)
+    count = int(n[0].item())
+    if count < 0:
+        raise RuntimeError("pair_overlaps: the planes changed between the two passes")
+    return pairs[:count]
+
+
+def merge_apply(a: torch.Tensor, b: torch.Tensor, winner: torch.Tensor, removed: torch.Tensor,
+                merged: Optional[torch.Tensor] = None, remaining: Optional[torch.Tensor] = None):
+    """One pass over two ``[H, W]`` int32 HBM planes with two int32 tables indexed by ``b``:
+    ``merged = winner[b] != 0 ? winner[b] : a`` and ``remaining = removed[b] ? 0 : b`` (int32 planes, any row stride)."""
+    h, w = _label_pair(a, b)
+    for name, t in (("winner", winner), ("removed", removed)):
+        if t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or not t.is_contiguous() or not t.numel():
+            raise ValueError("%s must be a contiguous int32 HBM vector" % name)
+    if winner.numel() != removed.numel():
+        raise ValueError("winner and removed must have one length")
+    merged = _label_plane(merged, h, w, a.device, "merged")
+    remaining = _label_plane(remaining, h, w, a.device, "remaining")
+    rc = _capi.lib().pxsom_merge_apply(a.data_ptr(), _ld(a), b.data_ptr(), _ld(b), h, w, winner.data_ptr(),
+                                       removed.data_ptr(), winner.numel(), merged.data_ptr(), _ld(merged),
+                                       remaining.data_ptr(), _ld(remaining), _capi.stream_ptr())
+    _capi.check(rc, "pxsom_merge_apply")
+    return merged, remaining
+
+
+def _region_tables(labels: torch.Tensor, n: int):
+    """count [n] int64, sums [n, 2] int64 (row, column) and bbox [n, 4] int32 (closed) of the labels 1 .. n, on the host."""
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros((0, 2), np.int64), np.zeros((0, 4), np.int32)
+    h, w, ld = _label_image(labels, "labels")
+    dev = labels.device
+    keys = torch.arange(1, n + 1, dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int64, device=dev)
+    sums = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    shape = torch.empty((n, 6), dtype=torch.int64, device=dev)
+    lib = _capi.lib()
+    wsb = lib.pxsom_region_shape_workspace_bytes(n, 1, n, 0)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    rc = lib.pxsom_region_shape(labels.data_ptr(), SEG_DTYPES[labels.dtype], ld, h, w, keys.data_ptr(), n, 1, n,
+                                shape.data_ptr(), count.data_ptr(), sums.data_ptr(), bbox.data_ptr(), ws.data_ptr(), wsb, 0,
+                                _capi.stream_ptr())
+    _capi.check(rc, "pxsom_region_shape")
+    return count.cpu().numpy(), sums.cpu().numpy(), bbox.cpu().numpy()
+
+
+def choose_merges(pairs: np.ndarray, object_bbox: np.ndarray, cell_count: np.ndarray, cell_sums: np.ndarray,
+                  overlap_thresh, expansion_factor):
+    """The choice of merge_masks_single on the host, in the reference's float64 statements.  ``pairs`` [P, 3] sorted by
+    (object, cell); ``object_bbox`` [n_o, 4] closed (row min, row max, column min, column max); ``cell_count`` [n_c] and
+    ``cell_sums`` [n_c, 2] of the cells 1 .. n_c.  Returns the int32 tables ``(winner, removed)`` of n_c + 1 entries:
+    the largest object that chose the cell (0: none) and whether any did.  A cell without overlap is never chosen, so
+    only the cells of the pair list are candidates; they come in ascending label within an object."""
+    n_c = len(cell_count)
+    winner = np.zeros(n_c + 1, dtype=np.int32)
+    removed = np.zeros(n_c + 1, dtype=np.int32)
+    if len(pairs) == 0:
+        return winner, removed
+    cells = pairs[:, 1].astype(np.int64) - 1
+    area = cell_count[cells].astype(np.int64)
+    centroid = cell_sums[cells].astype(np.float64) / area.astype(np.float64)[:, None]      # one division per axis
+    box = object_bbox[pairs[:, 0].astype(np.int64) - 1].astype(np.int64)
+    inside = ((centroid[:, 0] >= box[:, 0] - expansion_factor) & (centroid[:, 0] <= box[:, 1] + expansion_factor) &
+              (centroid[:, 1] >= box[:, 2] - expansion_factor) & (centroid[:, 1] <= box[:, 3] + expansion_factor))
+    overlap = pairs[:, 2].astype(np.int64)
+    meets = overlap / area > overlap_thresh / 100
+    best_object, best_overlap, best_cell = 0, 0, 0
+
+    def settle():
+        if best_cell:
+            winner[best_cell] = best_object       # objects ascend: the last to choose a cell keeps it
+            removed[best_cell] = 1
+
+    for obj, cell, ov, ok in zip(pairs[:, 0].tolist(), pairs[:, 1].tolist(), overlap.tolist(), (inside & meets).tolist()):
+        if obj != best_object:
+            settle()
+            best_object, best_overlap, best_cell = obj, 0, 0
+        if ok and ov > best_overlap:
+            best_overlap, best_cell = ov, cell
+    settle()
+    return winner, removed
+
+
+def merge_masks(object_mask: torch.Tensor, cell_mask: torch.Tensor, overlap_thresh, expansion_factor):
+    """The device chain of ``merge_masks_single`` on two ``[H, W]`` integer HBM masks of one shape -> ``(merged,
+    remaining)`` int32 planes in HBM.  Both masks are relabelled (:func:`label_regions`, 8-neighbourhood); every object,
+    in ascending order, takes the cell with the largest overlap among the cells whose centroid lies in the object's
+    closed bounding box grown by ``expansion_factor`` and whose ``overlap / area > overlap_thresh / 100`` (both compares
+    strict, the smaller label on a tie).  ``merged`` is the object labels with every chosen cell painted in its object's
+    label (the largest, when several chose it); ``remaining`` the relabelled cells without the chosen ones.  One small
+    read-back -- the pair list and the region tables -- serves the choice (:func:`choose_merges`)."""
+    if object_mask.shape != cell_mask.shape:
+        raise ValueError("Both masks must have the same shape")
+    objects, n_o, _ = label_regions(object_mask, 2)
+    cells, n_c, cell_areas = label_regions(cell_mask, 2)
+    n_o, n_c = int(n_o.item()), int(n_c.item())
+    pairs = pair_overlaps(objects, cells, n_o, n_c).cpu().numpy() if n_o and n_c else np.zeros((0, 3), np.int32)
+    if len(pairs):
+        _, _, object_bbox = _region_tables(objects, n_o)
+        _, cell_sums, _ = _region_tables(cells, n_c)
+        cell_count = cell_areas[1:n_c + 1].cpu().numpy()
+    else:
+        object_bbox, cell_sums, cell_count = np.zeros((n_o, 4), np.int32), np.zeros((n_c, 2), np.int64), np.ones(n_c, np.int64)
+    winner, removed = choose_merges(pairs, object_bbox, cell_count, cell_sums, overlap_thresh, expansion_factor)
+    dev = objects.device
+    return merge_apply(objects, cells, torch.from_numpy(winner).to(dev), torch.from_numpy(removed).to(dev))
+
+
 def zero_by_segmentation(img: torch.Tensor, seg: torch.Tensor, exclude: bool = True) -> torch.Tensor:
     """In place: ``img[seg > 0] = 0`` (``exclude``) or ``img[seg == 0] = 0`` for a contiguous HBM image (uint8, int16,
     uint16, int32 or float32) and a contiguous segmentation of the same shape (uint8 .. int64)."""

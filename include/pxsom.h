@@ -743,6 +743,50 @@ int pxsom_gaussian_blur_plane_mode(const void *in_dev, void *out_dev, void *tmp_
 int pxsom_binarize_plane(const void *plane_dev, int dtype, int h, int w, int mode, double level, const void *local_dev,
                          uint8_t *out_dev, int64_t ldo, void *stream);
 
+/* ---- merging ez_seg object masks into the cell segmentation (K18) -----------------------------------------------------
+ * reference: ark/segmentation/ez_seg/merge_masks.py merge_masks_single (skimage.morphology.label of both masks, one
+ * full-image logical_and per candidate cell of every object).  Symbols added under ABI 9, none changed.
+ *
+ * pxsom_label_regions: skimage.measure.label(img, background=0, connectivity) of an integer label plane: a component is
+ * a maximal set of pixels of ONE non-zero value joined under the 4- (connectivity 1) or 8-neighbourhood (2); touching
+ * regions of different values stay apart, a negative value is a label like any other.
+ *   seg_dev     [h, w] of a label dtype (PXSOM_SEG_U8 .. PXSOM_SEG_I64), row stride ld >= w elements
+ *   labels_dev, n_dev, areas_dev, capacity, workspace: as for pxsom_label_components, with the same numbering (by first
+ *               pixel in raster order) and the same stages after the tile and border passes; an image of one value gives
+ *               the bits pxsom_label_components gives.  capacity = h * w + 1 holds every image (a two-value checkerboard
+ *               under connectivity 1 makes every pixel a region).
+ *   Workspace: pxsom_label_regions_workspace_bytes(h, w).  Same error rules as pxsom_label_components.
+ *
+ * pxsom_pair_overlaps: the pairs of labels two planes share.  a_dev, b_dev [h, w] int32, row strides lda, ldb; a pixel
+ * belongs to the pair (a, b) when 1 <= a <= n_a and 1 <= b <= n_b -- any other value is counted nowhere and is never an
+ * index.  pairs_dev [capacity, 3] int32 receives one row (a, b, pixels) per pair with pixels > 0, sorted by (a, b); rows
+ * past the count are not written.  n_dev [2] int32: n_dev[1] = the RUNS of the image -- stretches of one pair inside a row
+ * and inside an aligned group of 64 pixels of the flat raster order -- which bounds the number of distinct pairs;
+ * n_dev[0] = the number of pairs, or -1 (and nothing written to pairs_dev) when the runs exceed capacity.
+ *   Called with pairs_dev == NULL (capacity, workspace ignored) only the runs are counted: n_dev = {0, runs}; a caller
+ *   sizes pairs_dev and the workspace from that and calls again.  The table behind the list has >= 2 * capacity slots and
+ *   takes one insertion per run, and none when runs > capacity: it cannot overflow whatever the planes hold.  No dense
+ *   n_a x n_b table, integer atomics only, a sort of the table: the same input gives the same bytes on every run.
+ *   Workspace: pxsom_pair_overlaps_workspace_bytes(capacity) (0 for a capacity outside 1 .. 2^27).
+ *
+ * pxsom_merge_apply: one pass over both planes with two int32 tables of `table` entries (indexed by b):
+ *   merged[p]    = winner[b[p]] != 0 ? winner[b[p]] : a[p]
+ *   remaining[p] = removed[b[p]] != 0 ? 0 : b[p]
+ * a b[p] outside [0, table) has no winner and is not removed.  All four planes [h, w] int32 with their own row strides.
+ * Bad sizes, strides, counts, capacity, pointers or workspace: PXSOM_ERR_INVALID_ARG, the limit in the message, before
+ * any HIP call, for all three entries. */
+size_t pxsom_label_regions_workspace_bytes(int h, int w);
+int pxsom_label_regions(const void *seg_dev, int dtype, int h, int w, int64_t ld, int connectivity, int32_t *labels_dev,
+                        int64_t ldo, int32_t *n_dev, int32_t *areas_dev, int64_t capacity, void *workspace_dev,
+                        size_t workspace_bytes, void *stream);
+size_t pxsom_pair_overlaps_workspace_bytes(int64_t capacity);
+int pxsom_pair_overlaps(const int32_t *a_dev, int64_t lda, const int32_t *b_dev, int64_t ldb, int h, int w, int32_t n_a,
+                        int32_t n_b, int32_t *pairs_dev, int64_t capacity, int32_t *n_dev, void *workspace_dev,
+                        size_t workspace_bytes, void *stream);
+int pxsom_merge_apply(const int32_t *a_dev, int64_t lda, const int32_t *b_dev, int64_t ldb, int h, int w,
+                      const int32_t *winner_dev, const int32_t *removed_dev, int64_t table, int32_t *merged_dev, int64_t ldm,
+                      int32_t *remaining_dev, int64_t ldr, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
