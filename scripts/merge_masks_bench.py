@@ -23,7 +23,9 @@ from tests import merge_masks_reference as mmr  # noqa: E402
 
 def masks(rs, size, n_cells, n_objects):
     scale = size / 2048.0
-    return mmr.random_masks(rs, size, size, n_cells, n_objects, cell_r=(6, 12), object_r=(max(8, int(20 * scale)), max(12, int(45 * scale))))
+    # (the windowed painter: the same masks as random_masks, without a whole-image pass per disc)
+    return mmr.random_masks_windowed(rs, size, size, n_cells, n_objects, cell_r=(6, 12),
+                                     object_r=(max(8, int(20 * scale)), max(12, int(45 * scale))))
 
 
 def timed(fn, reps):

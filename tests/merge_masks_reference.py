@@ -102,3 +102,21 @@ def random_masks(rs, h, w, n_cells, n_objects, cell_r=(2, 5), object_r=(3, 8)):
     for i in range(n_objects):
         objects[disc((h, w), (rs.randint(h), rs.randint(w)), rs.randint(object_r[0], object_r[1] + 1) ** 2)] = i + 1
     return objects, cells
+
+
+def random_masks_windowed(rs, h, w, n_cells, n_objects, cell_r=(2, 5), object_r=(3, 8)):
+    """:func:`random_masks`, draw for draw, with every disc painted inside its bounding window only: the cost of a disc
+    no longer grows with the image (the field-size tests)."""
+    def paint(plane, value, radii):
+        cy, cx, r = rs.randint(h), rs.randint(w), rs.randint(radii[0], radii[1] + 1)
+        y0, y1, x0, x1 = max(cy - r, 0), min(cy + r + 1, h), max(cx - r, 0), min(cx + r + 1, w)
+        rr, cc = np.mgrid[y0:y1, x0:x1]
+        plane[y0:y1, x0:x1][(rr - cy) ** 2 + (cc - cx) ** 2 < r ** 2] = value
+
+    cells = np.zeros((h, w), dtype=np.int32)
+    for i in range(n_cells):
+        paint(cells, rs.randint(1, n_cells + 1), cell_r)        # (the value is drawn before the disc, as an assignment does)
+    objects = np.zeros((h, w), dtype=np.int32)
+    for i in range(n_objects):
+        paint(objects, i + 1, object_r)
+    return objects, cells

@@ -77,6 +77,19 @@ def test_statement_on_the_two_disc_case():
     assert pairs[2, 4] > pairs[2, 3] > 0.10 * area
 
 
+@pytest.mark.parametrize("h,w,n_cells,n_objects", [(40, 57, 30, 6), (1, 90, 10, 3), (130, 65, 140, 20), (7, 3, 5, 2)])
+def test_windowed_discs_equal_whole_image_discs(h, w, n_cells, n_objects):
+    """random_masks_windowed (the field-size GPU tests) paints what random_masks paints, from the same draws: discs cut
+    by every border, discs wider than the image, and the generator left in the same state."""
+    for radii in (dict(), dict(cell_r=(6, 14), object_r=(10, 30))):
+        rs_whole, rs_window = np.random.RandomState(h + w), np.random.RandomState(h + w)
+        whole = mmr.random_masks(rs_whole, h, w, n_cells, n_objects, **radii)
+        window = mmr.random_masks_windowed(rs_window, h, w, n_cells, n_objects, **radii)
+        assert np.array_equal(whole[0], window[0]) and np.array_equal(whole[1], window[1])
+        assert whole[0].dtype == window[0].dtype and whole[1].dtype == window[1].dtype
+        assert rs_whole.randint(1 << 30) == rs_window.randint(1 << 30)
+
+
 # ---- hand-built cases, one quirk each ---------------------------------------------------------------------------------------
 def quirks():
     """name -> (object mask, cell mask, overlap_thresh, expansion_factor); used by the GPU test too."""
