@@ -6,7 +6,8 @@ reads one N x N distance matrix per FOV from ``dist_mat_dir``; here that directo
 ``generate_cluster_matrix_results`` runs k-means over the counts on the host and builds the reference's three tables; its
 first frame carries the ``kmeans_neighborhood`` column that ``utils.data_utils.generate_and_save_neighborhood_cluster_masks``
 consumes.  Between the two, ``compute_cluster_metrics_inertia`` and ``compute_cluster_metrics_silhouette`` sweep k: the
-fits on the host, the silhouette scores of every k from one device call (pxsom_silhouette); they return a
+fits on the host (or, with ``kmeans="device"`` in any of the three, in one pxsom_kmeans_lloyd call: DESIGN.md K19), the
+silhouette scores of every k from one device call (pxsom_silhouette); they return a
 ``pandas.Series`` indexed by ``cluster_num`` where the reference returns an ``xarray.DataArray``.
 
 The notebook's other two steps, the cell-distance and the diversity analysis, are in ``cell_neighborhood_stats``.
@@ -93,8 +94,9 @@ def create_neighborhood_matrix(all_data, dist_mat_dir=None, included_fovs=None, 
 def generate_cluster_matrix_results(all_data, neighbor_mat, cluster_num, seed=42, excluded_channels=None,
                                     included_fovs=None, cluster_label_col=_KMEANS_CLUSTER, fov_col=_FOV_ID,
                                     cell_type_col=_CELL_TYPE, label_col=_CELL_LABEL, pre_channel_col=_CELL_SIZE,
-                                    post_channel_col=_CELL_LABEL):
-    """k-means over the neighbourhood matrix (on the host), then the reference's three tables:
+                                    post_channel_col=_CELL_LABEL, *, kmeans="host"):
+    """k-means over the neighbourhood matrix (on the host, or with ``kmeans="device"`` its ten restarts in one device
+    call: DESIGN.md K19), then the reference's three tables:
 
     - ``all_data`` restricted to the included FOVs and to cells of ``neighbor_mat``, with ``cluster_label_col`` attached;
     - clusters x phenotypes: how many cells of each phenotype a cluster holds (index ``Cluster<k>``);
@@ -103,6 +105,7 @@ def generate_cluster_matrix_results(all_data, neighbor_mat, cluster_num, seed=42
 
     The labels come from ``spatial_analysis_utils.generate_cluster_labels``.
     """
+    spatial_analysis_utils._check_kmeans(kmeans)
     if included_fovs is None:
         included_fovs = neighbor_mat[fov_col].unique()
     verify_in_list(fov_names=included_fovs, unique_fovs=all_data[fov_col].unique())
@@ -112,8 +115,9 @@ def generate_cluster_matrix_results(all_data, neighbor_mat, cluster_num, seed=42
         raise ValueError("Invalid k provided for clustering")
 
     mat = neighbor_mat[neighbor_mat[fov_col].isin(included_fovs)].copy()
+    route = {} if kmeans == "host" else {"kmeans": kmeans}      # the default call is the one it has always been
     mat[cluster_label_col] = spatial_analysis_utils.generate_cluster_labels(
-        mat.drop([fov_col, label_col, cell_type_col], axis=1), cluster_num, seed=seed)
+        mat.drop([fov_col, label_col, cell_type_col], axis=1), cluster_num, seed=seed, **route)
 
     clustered = all_data[all_data[fov_col].isin(included_fovs)].merge(
         mat[[fov_col, label_col, cluster_label_col]], on=[fov_col, label_col])
@@ -145,18 +149,23 @@ def _sweep_data(neighbor_mat, min_k, max_k, included_fovs, fov_col, label_col, c
 
 
 def compute_cluster_metrics_inertia(neighbor_mat, min_k=2, max_k=10, seed=42, included_fovs=None, fov_col=_FOV_ID,
-                                    label_col=_CELL_LABEL, cell_col=_CELL_TYPE):
+                                    label_col=_CELL_LABEL, cell_col=_CELL_TYPE, *, kmeans="host"):
     """The k-means inertia of the neighbourhood matrix for every k of ``min_k .. max_k`` (both at least 2), over the
-    rows of ``included_fovs`` (default: all).  Returns ``spatial_analysis_utils.compute_kmeans_inertia``'s Series."""
+    rows of ``included_fovs`` (default: all); ``kmeans`` is passed down.  Returns
+    ``spatial_analysis_utils.compute_kmeans_inertia``'s Series."""
+    spatial_analysis_utils._check_kmeans(kmeans)
     data = _sweep_data(neighbor_mat, min_k, max_k, included_fovs, fov_col, label_col, cell_col)
-    return spatial_analysis_utils.compute_kmeans_inertia(neighbor_mat_data=data, min_k=min_k, max_k=max_k, seed=seed)
+    return spatial_analysis_utils.compute_kmeans_inertia(neighbor_mat_data=data, min_k=min_k, max_k=max_k, seed=seed,
+                                                        kmeans=kmeans)
 
 
 def compute_cluster_metrics_silhouette(neighbor_mat, min_k=2, max_k=10, seed=42, included_fovs=None, fov_col=_FOV_ID,
-                                       label_col=_CELL_LABEL, cell_col=_CELL_TYPE, subsample=None):
+                                       label_col=_CELL_LABEL, cell_col=_CELL_TYPE, subsample=None, *,
+                                       kmeans="host"):
     """The silhouette score of the k-means clusters of the neighbourhood matrix for every k of ``min_k .. max_k`` (both
     at least 2), over the rows of ``included_fovs`` (default: all); ``subsample`` rows per cluster are scored when it is
-    given.  Returns ``spatial_analysis_utils.compute_kmeans_silhouette``'s Series."""
+    given; ``kmeans`` is passed down.  Returns ``spatial_analysis_utils.compute_kmeans_silhouette``'s Series."""
+    spatial_analysis_utils._check_kmeans(kmeans)
     data = _sweep_data(neighbor_mat, min_k, max_k, included_fovs, fov_col, label_col, cell_col)
     return spatial_analysis_utils.compute_kmeans_silhouette(neighbor_mat_data=data, min_k=min_k, max_k=max_k, seed=seed,
-                                                            subsample=subsample)
+                                                            subsample=subsample, kmeans=kmeans)

@@ -686,6 +686,36 @@ int pxsom_silhouette(const double *x_dev, int64_t n, int d, const int32_t *label
                      int n_labelings, int k, int32_t *counts_dev, double *sums_dev, double *samples_dev,
                      double *scores_dev, void *stream);
 
+/* ---- Lloyd's k-means of the rows of a matrix for several problems at once (K19) ---------------------------------------
+ * reference: sklearn.cluster.KMeans (Lloyd) as ark/analysis/spatial_analysis_utils.py fits it: once per k of a sweep, or
+ * with ten restarts.  Every (k, restart) is one problem over the same rows; one iteration is one pass over the rows per
+ * group of still-active problems (the grouping rule and its LDS bytes: csrc/pxsom_kmeans.hip).  Symbols added under ABI
+ * 9, none changed.
+ *   x_dev          [n, d] binary64, row-major, finite; 1 <= d <= 64, n < 2^31
+ *   k_host         [n_problems] int32 on the host, every k in 1 .. 32 and <= n; 1 <= n_problems <= 4096
+ *   centres_dev    [sum of k, d] binary64: problem p's rows follow those of problem p - 1.  In: the initial centres.
+ *                  Out: the final ones.
+ *   tol_host       [n_problems] binary64 >= 0, max_iter_host [n_problems] int32 >= 1, on the host
+ *   labels_dev     [n_problems, n] int32, written: 0 .. k_p - 1
+ *   inertia_host   [n_problems] binary64, iters_host [n_problems] int32, written on the host
+ *   workgroups     0: twice the CU count; otherwise the grid of the assignment kernel (the results do not depend on it)
+ * The rule: distance = sum_j (x_j - c_j)^2 with j ascending and every operation rounded on its own (no
+ * fused multiply-add), first minimum wins; sums over fixed blocks of 256 rows folded in block order (no floating-point
+ * atomic: the same input gives the same bits for any grid and any grouping); centre = sum / count; an empty cluster
+ * moves to the row farthest from its own centre (several: ascending clusters take the farthest rows in order, ties to the
+ * lower row); a problem stops when no label changed, or after one closing assignment pass when
+ * sum ||new - old||^2 <= tol or max_iter is reached; inertia is the sum of the winning distances of the last
+ * assignment.  n = 0 returns at once (iterations and inertia 0, nothing else written).  The call synchronises the stream
+ * once per iteration to read three numbers per problem.  Workspace: pxsom_kmeans_workspace_bytes (0 for sizes the entry
+ * does not take).  pxsom_kmeans_group_count: how many groups, so passes over the rows, the first iteration of these
+ * problems takes (a host-side function; a negative status for bad sizes).  Sizes outside the limits, k > n, a bad tol
+ * or max_iter, null pointers: PXSOM_ERR_INVALID_ARG before any HIP call; a short workspace: PXSOM_ERR_WORKSPACE. */
+size_t pxsom_kmeans_workspace_bytes(int64_t n, int d, int n_problems, const int32_t *k_host);
+int pxsom_kmeans_group_count(int d, int n_problems, const int32_t *k_host);
+int pxsom_kmeans_lloyd(const double *x_dev, int64_t n, int d, int n_problems, const int32_t *k_host, double *centres_dev,
+                       const double *tol_host, const int32_t *max_iter_host, int32_t *labels_dev, double *inertia_host,
+                       int32_t *iters_host, void *workspace_dev, size_t workspace_bytes, int workgroups, void *stream);
+
 /* ---- object masks: connected-component labelling and the passes around it (K16) --------------------------------------
  * reference: ark/segmentation/ez_seg/ez_object_segmentation.py _create_object_mask (filters.gaussian, a threshold,
  * morphology.remove_small_holes, measure.label(connectivity=2), regionprops_table area, map_array), which
