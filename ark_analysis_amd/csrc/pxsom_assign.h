@@ -208,6 +208,8 @@ struct StepArgs {
     unsigned *xch_ticket = nullptr;
     int xch_nranks = 0, xch_rank = 0;
     unsigned long long xch_max_count = 0, xch_wait = 0, xch_signal = 0;
+    // duplicate test of the fused step (PXSOM_TRAIN_SMALL_DUP_TABLES): 4 buckets per table -- every node takes the linear scan
+    int dup_small = 0;
 };
 
 // round-half-even to the quantum behind qmagic (exact while |v| < 2^51 q)

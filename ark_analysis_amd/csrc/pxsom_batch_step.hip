@@ -11,6 +11,10 @@
 //     them: thread <-> (node, lane group q) holds exactly the channels of one MFMA A-fragment element, so norms,
 //     the duplicate key, the fp16 hi/lo split and the fragment store need no further LDS round trip;
 //   * the rows of the step are requested before any of that (they do not depend on the codebook);
+//   * exact duplicates of an earlier node are masked out of the filter (windowed steps only) without an all-pairs search: two
+//     bucket tables in LDS keep the first node index per bucket of the key (ds_min_u32 in P3); a node that finds itself in either
+//     table has no earlier twin, a first node that holds the key is compared channel by channel, and the linear key scan is left
+//     for nodes that collide with other keys in both tables (PXSOM_TRAIN_SMALL_DUP_TABLES: 4 buckets, every node scans);
 //   * BMU search: fp16-split MFMA filter (the K7 scheme: v_mfma_f32_16x16x32_f16, nodes on the M axis, running
 //     top-2 with the node id in the low mantissa bits, rigorous tolerance) on 16-row tiles, TPW tiles per wave;
 //     rows it is sure of go straight into the workgroup's binary64 table in LDS (ds_add_f64); rows it is not sure
@@ -33,6 +37,10 @@ __device__ long long g_block_ticks[2 * 256];   // per workgroup: first and last 
 #endif
 
 constexpr int kStepThreads = 512, kStepWaves = 8;
+// Buckets per table of the duplicate test (a power of two).  100 nodes in 2 048 buckets: node i finds an EARLIER node of another
+// key in its bucket with probability ~i / 2048 per table, in both (the only case that falls back to the scan) ~(i / 2048)^2 --
+// 0.08 nodes per codebook, and every workgroup sees the same codebook.
+constexpr int kDupBuckets = 2048;
 // Copies of the workgroup's statistics table (pixel lane pix adds into copy pix % copies) against same-word contention of
 // the ds_add_f64 lanes while the codebook is crowded.  Measured in round 3 with 4 copies: the crowded head steps did not
 // move (36.0 / 33.1 us before and after: the LDS serialisation is not what holds them) and every step paid for clearing and
@@ -45,7 +53,7 @@ __host__ __device__ inline int table_stride(int c) { return c | 1; }
 
 // LDS carve-up (bytes from the start of the dynamic segment)
 struct StepLds {
-    size_t ls, wt, tl, key, red, ovf, frag, bias, hdr, mu, total;
+    size_t ls, wt, tl, key, red, ovf, frag, bias, hdr, mu, dup, total;
 };
 __host__ __device__ inline StepLds step_lds(int c)
 {
@@ -61,6 +69,9 @@ __host__ __device__ inline StepLds step_lds(int c)
     L.bias = o;  o += (size_t)kNB * 64 * 16;              // [NB][64] f32x4
     L.hdr = o;   o += 64;
     L.mu = o;    o += 40 * 4;                             // the run's centring vector (32 words) and its norm (word 32)
+    // duplicate test of the windowed steps: first node index per key bucket, two tables.  (The BMU-only kernels do not touch it but
+    // are launched with the same size: a CU holds one workgroup of a step by design -- launch_step --, so the 16 KB cost nothing.)
+    L.dup = o;   o += (size_t)2 * kDupBuckets * 4;
     L.total = o;
     return L;
 }
@@ -91,6 +102,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
     f32x4 *bias_l = reinterpret_cast<f32x4 *>(step_smem + L.bias);
     StepHdr *hdr = reinterpret_cast<StepHdr *>(step_smem + L.hdr);
     float *mu_l = reinterpret_cast<float *>(step_smem + L.mu);
+    unsigned *dup_l = reinterpret_cast<unsigned *>(step_smem + L.dup);
 
     constexpr int NP = CPL / 2;
     typedef typename Pair<T>::type P2;
@@ -150,6 +162,10 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
     const int NC = c + 1;
     auto load_centring = [&]() {
         if (tid < 33 && sa.mu32) mu_word = sa.mu32[tid < 32 ? tid : kFilterMaxChannels];   // 32 channels + the vector's norm
+    };
+    auto clear_dup_tables = [&]() {   // all ones: no node yet
+        if constexpr (!BMU)
+            for (int e = tid; e < 2 * kDupBuckets / 4; e += kStepThreads) reinterpret_cast<uint4 *>(dup_l)[e] = uint4{~0u, ~0u, ~0u, ~0u};
     };
     auto park_centring = [&]() {
         if (tid < 40) mu_l[tid] = mu_word;
@@ -240,6 +256,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             hdr->bad = 0;
         }
         if (tid < 64) bias_l[6 * 64 + tid] = f32x4{kNegBig, kNegBig, kNegBig, kNegBig};   // rows of the last block without a node
+        clear_dup_tables();
         if (sa.stats_zero) {
             const int per = (sa.zero_count + (int)gridDim.x - 1) / (int)gridDim.x;
             const int z1 = min(((int)blockIdx.x + 1) * per, sa.zero_count);
@@ -278,6 +295,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             hdr->bad = 0;
         }
         if (tid < 64) bias_l[6 * 64 + tid] = f32x4{kNegBig, kNegBig, kNegBig, kNegBig};   // rows of the last block without a node
+        clear_dup_tables();
         if (sa.stats_zero) {
             const int per = (sa.zero_count + (int)gridDim.x - 1) / (int)gridDim.x;
             const int z1 = min(((int)blockIdx.x + 1) * per, sa.zero_count);
@@ -343,6 +361,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             hdr->bad = 0;
         }
         if (tid < 64) bias_l[6 * 64 + tid] = f32x4{kNegBig, kNegBig, kNegBig, kNegBig};   // rows of the last block without a node
+        clear_dup_tables();
         if (sa.stats_zero) {
             const int per = (sa.zero_count + (int)gridDim.x - 1) / (int)gridDim.x;
             const int z1 = min(((int)blockIdx.x + 1) * per, sa.zero_count);
@@ -359,6 +378,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
     for (int i = 0; i < CPL; i++) mud32[i] = mu_l[nq * CPL + i < 32 ? nq * CPL + i : 0];
     const float mu_norm = mu_l[32];
     unsigned long long kkey = 0;
+    unsigned dup_b1 = 0, dup_b2 = 0;   // this node's buckets of the duplicate test
     {
         bool bad = false;
         if (has_node) {
@@ -415,6 +435,17 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             kkey ^= __shfl_xor(kkey, 1);
             kkey ^= __shfl_xor(kkey, 2);
             if (has_node && nq == 0) key[node] = kkey;
+            {
+                // two buckets per key, from its two halves: equal keys share both, and ds_min_u32 leaves the FIRST node of each
+                const unsigned dmask = sa.dup_small ? 3u : (unsigned)kDupBuckets - 1u;
+                const unsigned klo = (unsigned)kkey, khi = (unsigned)(kkey >> 32);
+                dup_b1 = (klo ^ (klo >> 11) ^ (klo >> 22)) & dmask;
+                dup_b2 = (khi ^ (khi >> 11) ^ (khi >> 22)) & dmask;
+                if (has_node && nq == 0) {
+                    (void)__hip_atomic_fetch_min(dup_l + dup_b1, (unsigned)node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    (void)__hip_atomic_fetch_min(dup_l + kDupBuckets + dup_b2, (unsigned)node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
         }
         if (bad) hdr->bad = 1;   // NaN / Inf in the codebook: every row takes the exact path
         // the two maxima only steer the scale (the exponent of the largest magnitude) and the norm bound (rounded up by a hair
@@ -479,9 +510,8 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             const int lf = (nq << 4) | m;
             frag_l[(b * 2 + 0) * 64 + lf] = fhi;
             frag_l[(b * 2 + 1) * 64 + lf] = flo;
-            // Exact duplicates of an EARLIER node are masked out of the filter (pxsom_prep.h).  The node's 4 lanes scan
-            // the earlier nodes' keys together (lane nq takes prev = nq, nq + 4, ...; no early exit, so the LDS reads
-            // pipeline), the smallest match is then compared channel by channel.
+            // Exact duplicates of an EARLIER node are masked out of the filter (pxsom_prep.h): a node is masked if and only if
+            // an earlier node has its key and compares equal in every channel.
             auto same_as = [&](int prev) {   // all channels equal, decided by the node's 4 lanes together
                 bool eq = true;
 #pragma unroll
@@ -496,16 +526,36 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             };
             // (BMU-only steps do not look for duplicates: the first of two equal nodes takes all their rows and moves away
             // within a step; until then their rows are listed and settled exactly -- the labels do not depend on the mask)
-            int hit = 0x7fffffff;
+            // The all-pairs scan: the node's 4 lanes scan the earlier nodes' keys together (lane nq takes prev = nq, nq + 4, ...;
+            // no early exit, so the LDS reads pipeline), the smallest match is then compared channel by channel.
+            auto scan_dups = [&]() {
+                int hit = 0x7fffffff;
 #pragma unroll 5
-            for (int prev = nq; prev < (bmu_only ? 0 : kK); prev += 4) hit = min(hit, (prev < node && key[prev] == kkey) ? prev : 0x7fffffff);
-            hit = min(hit, __shfl_xor(hit, 1));
-            hit = min(hit, __shfl_xor(hit, 2));
+                for (int prev = nq; prev < kK; prev += 4) hit = min(hit, (prev < node && key[prev] == kkey) ? prev : 0x7fffffff);
+                hit = min(hit, __shfl_xor(hit, 1));
+                hit = min(hit, __shfl_xor(hit, 2));
+                bool d = false;
+                if (hit != 0x7fffffff) {
+                    d = same_as(hit);
+                    for (int prev = hit + 1; prev < node && !d; prev++)   // a key collision: keep looking
+                        if (key[prev] == kkey) d = same_as(prev);
+                }
+                return d;
+            };
             bool dup = false;
-            if (hit != 0x7fffffff) {
-                dup = same_as(hit);
-                for (int prev = hit + 1; prev < node && !dup; prev++)   // a key collision: keep looking
-                    if (key[prev] == kkey) dup = same_as(prev);
+            if constexpr (!BMU) {
+                // The scan ran in every workgroup of every windowed step (25 dependent LDS reads per lane, ~1.5 us of the chain) to
+                // find what a handful of nodes can be.  Instead: m1, m2 = the first node in each of this key's two buckets (the node
+                // put itself there in P3, so m <= node).  m == node in either table: no earlier node has the key -- not a duplicate.
+                // Otherwise a minimum that HOLDS the key is the first node with it: equal in every channel -- a duplicate.  Only a
+                // node whose two minima both hold other keys, or whose key match is not an equal node (a key collision, NaN),
+                // still scans.  All 4 lanes of a node take the same branches (same key, same minima).
+                const unsigned m1 = dup_l[dup_b1], m2 = dup_l[kDupBuckets + dup_b2];
+                if (m1 < (unsigned)node && m2 < (unsigned)node) {
+                    const int m = (int)(key[m1] == kkey ? m1 : m2);
+                    if (key[m] == kkey) dup = same_as(m);
+                    if (!dup) dup = scan_dups();
+                }
             }
             // bias of accumulator row m = 4 qf + rr of block b, replicated over the 16 pixel lanes: this lane writes 4
             const float bvv = dup ? kNegBig : (float)(-0.5 * nrm * scale * scale);
@@ -1151,7 +1201,8 @@ int launch_step(const T *x, int64_t n, int c, int64_t ldx, double *stats, const 
     // 16-row tiles per wave: one for the steps that fit the chip in one round (a step is latency, the shortest chain wins:
     // measured on 16 K-row steps, 0.93 ms per 64-step pass against 0.99 with two); the large steps of a schedule take 2 or
     // 4 -- a round costs ~3.5 us whatever it holds, and the search itself runs at a fraction of the filter kernel's rate
-    // workgroup slots: one per CU.  (Two fit -- 77 KB of LDS, <= 128 VGPRs each -- and were measured on the two-phase
+    // workgroup slots: one per CU.  (Two fitted while the step took 77 KB of LDS -- it takes 93 KB at c = 22 since the duplicate
+    // tables --, <= 128 VGPRs each, and were measured on the two-phase
     // schedule's large steps: SLOWER, pass 0.505 -> 0.574 ms; a step's time grows with the number of workgroups that flush
     // their tables into the same 18 KB of statistics.)
     const int64_t cus = pxsom::device_cu_count(), slots = cus;

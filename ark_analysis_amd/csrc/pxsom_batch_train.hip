@@ -498,6 +498,7 @@ int train_steps_typed(const T *x, int64_t n, int c, int64_t ldx, int dtype, doub
             sa.qmagic = qmagic;
             sa.group_w = wd > 1 ? wd : 1;
             sa.group_stride = (int64_t)sc.phases * ldx;
+            sa.dup_small = (flags & PXSOM_TRAIN_SMALL_DUP_TABLES) ? 1 : 0;
             if (fused_xch) {
                 const int i = gg - g_begin;                       // the exchange behind step gg has epoch base + i + 1
                 sa.xch_peers = fxch.peers;

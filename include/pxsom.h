@@ -228,6 +228,9 @@ int pxsom_batch_update_prepare(double *w_dev, int xdim, int ydim, int c, double 
 #define PXSOM_TRAIN_UNFUSED 1
 /* (flag value 2 was PXSOM_TRAIN_PERSISTENT_TAIL in ABI 6 - 8: an opt-in persistent launch for the BMU-only tail, measured slower
  * than the launches it replaced and removed in ABI 9; the bit is ignored.) */
+/* A test switch of the fused 10 x 10 step (csrc/pxsom_batch_step.hip): the two bucket tables of its duplicate-node test
+ * shrink to 4 buckets each, so that every node collides and the linear scan behind the tables runs.  Same results. */
+#define PXSOM_TRAIN_SMALL_DUP_TABLES 4
 size_t pxsom_batch_train_workspace_bytes(int64_t n, int batch_steps, int c, int k);
 int pxsom_batch_train_steps(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, double *wbuf_dev,
                             double *stats_ring_dev, int xdim, int ydim, int batch_steps, int g_begin, int g_end,

@@ -63,7 +63,18 @@ int main(int argc, char **argv)
                 {
                     long long bt[512];
                     hipMemcpyFromSymbol(bt, HIP_SYMBOL(g_block_ticks), sizeof(bt));
-                    const int nwg = std::min(256, (int)((rows + (tpw <= 1 ? 127 : 255)) / (tpw <= 1 ? 128 : 256)));
+                    // the grid launch_step chose (tiles per wave by step size, the fewest rounds spread evenly): entries past it
+                    // are another launch's, on another base of the 100 MHz counter -- the head steps' spreads were garbage
+                    int cus = 256;
+                    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0);
+                    const int64_t blocks1 = (rows + 127) / 128;
+                    int tiles = tpw == 2 ? 2 : (tpw == 4 ? 4 : 1);
+                    if (tpw <= 0) tiles = blocks1 <= cus ? 1 : (blocks1 <= 2 * (int64_t)cus ? 2 : 4);
+                    if (tiles == 4 && g > 0 && thr < 1.0) tiles = 2;
+                    const int64_t nblk = std::max<int64_t>((rows + 128 * tiles - 1) / (128 * tiles), 1), rounds = (nblk + cus - 1) / cus;
+                    const int nwg = (int)((nblk + rounds - 1) / rounds);
+                    const long long base = bt[0];   // every stamp relative to workgroup 0's start
+                    for (int b = 0; b < 2 * nwg; b++) bt[b] -= base;
                     long long s0 = bt[0], s1 = bt[0], e0 = bt[1], e1 = bt[1];
                     double dsum = 0;
                     for (int b = 0; b < nwg; b++) {
