@@ -117,7 +117,8 @@ SYMBOLS = {
                                   _vp, _vp, _sz, _i32, _vp]),
     "pxsom_region_hull": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp]),
     "pxsom_neighbor_counts": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _vp, _vp]),
-    "pxsom_nearest_type_means": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f64, _vp, _vp]),
+    "pxsom_close_pair_counts": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _f64, _f64, _i32, _vp, _vp]),
+    "pxsom_nearest_type_means":(_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f64, _vp, _vp]),
     "pxsom_silhouette": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pxsom_kmeans_workspace_bytes": (_sz, [_i64, _i32, _i32, _vp]),
     "pxsom_kmeans_group_count": (_i32, [_i32, _i32, _vp]),

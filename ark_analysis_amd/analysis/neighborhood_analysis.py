@@ -12,8 +12,13 @@ silhouette scores of every k from one device call (pxsom_silhouette, DESIGN.md K
 
 The notebook's other two steps, the cell-distance and the diversity analysis, are in ``cell_neighborhood_stats``.
 
-Not mirrored: ``calc_dist_matrix`` and the ``.xr`` files (xarray is not a dependency here), the enrichment statistics,
-the mixing scores and the plots."""
+The mixing-score notebook: ``compute_cell_ratios`` and ``compute_mixing_score`` are the reference's, host code over a
+neighbourhood matrix; ``compute_mixing_scores`` gives the scores of a whole cohort straight from the cell table -- the
+target / reference interaction totals of every FOV are one pxsom_close_pair_counts launch with two sets,
+so neither the distance files nor the neighbourhood matrix are needed.
+
+Not mirrored: ``calc_dist_matrix`` and the ``.xr`` files (xarray is not a dependency here), the enrichment statistics
+and the plots."""
 import warnings
 
 import numpy as np
@@ -169,3 +174,143 @@ def compute_cluster_metrics_silhouette(neighbor_mat, min_k=2, max_k=10, seed=42,
     data = _sweep_data(neighbor_mat, min_k, max_k, included_fovs, fov_col, label_col, cell_col)
     return spatial_analysis_utils.compute_kmeans_silhouette(neighbor_mat_data=data, min_k=min_k, max_k=max_k, seed=seed,
                                                             subsample=subsample, kmeans=kmeans)
+
+
+# ---- mixing scores --------------------------------------------------------------------------------------------------
+_MIXING_TYPES = ("percent", "homogeneous")
+
+
+def _check_populations(target_cells, reference_cells, mixing_type=None):
+    overlap = [cell for cell in target_cells if cell in reference_cells]
+    if overlap:
+        raise ValueError("The following cell types were included in both the target and reference populations: %s"
+                         % overlap)
+    if mixing_type is not None and mixing_type not in _MIXING_TYPES:
+        raise ValueError('Please provide a valid mixing_type: "percent" or "homogeneous".')
+
+
+def _mixing_exit(target_total, ref_total, ratio_threshold, cell_count_thresh):
+    """The reference's three NaN exits, in its order: too few cells, a population absent, a ratio over the threshold."""
+    if target_total + ref_total < cell_count_thresh:
+        return True
+    if ref_total == 0 or target_total == 0:
+        return True
+    return ref_total / target_total > ratio_threshold or target_total / ref_total > ratio_threshold
+
+
+def _mixing_quotient(reference_target, target_target, reference_reference, mixing_type):
+    """The score from the three interaction totals, divided as numpy divides float64 (0 / 0 is NaN)."""
+    mixed = np.float64(reference_target)
+    if mixing_type == "percent":
+        return mixed / (mixed + np.float64(target_target))
+    return mixed / (np.float64(target_target) + np.float64(reference_reference))
+
+
+def compute_cell_ratios(neighbors_mat, target_cells, reference_cells, fov_list, bin_number=10, cell_col=_CELL_TYPE,
+                        fov_col=_FOV_ID, label_col=_CELL_LABEL):
+    """Per FOV of ``fov_list``, the number of target cells over the number of reference cells among the rows of the
+    neighbourhood matrix ``neighbors_mat``; NaN where either population is absent.
+
+    Returns the reference's ``ratio_data`` frame: columns ``fov`` and ``cell_ratio``.  The reference also draws two
+    box plots and two histograms of the ratios; plotting stays out of this package, so ``bin_number`` (the histograms'
+    bins) is accepted and unused."""
+    verify_in_list(provided_column_names=[cell_col, fov_col, label_col], cell_neighbors_columns=neighbors_mat.columns)
+    ratios = []
+    for fov in fov_list:
+        types = neighbors_mat.loc[neighbors_mat[fov_col] == fov, cell_col]
+        target_total, reference_total = int(types.isin(target_cells).sum()), int(types.isin(reference_cells).sum())
+        ratios.append(np.nan if target_total == 0 or reference_total == 0 else target_total / reference_total)
+    return pd.DataFrame({"fov": list(fov_list), "cell_ratio": np.asarray(ratios, dtype=np.float64)})
+
+
+def compute_mixing_score(fov_neighbors_mat, target_cells, reference_cells, mixing_type, ratio_threshold=5,
+                         cell_count_thresh=200, cell_col=_CELL_TYPE, fov_col=_FOV_ID, label_col=_CELL_LABEL):
+    """The mixing score of one FOV from its rows of the neighbourhood matrix (host code, as in the reference).
+
+    With rt the neighbours of reference phenotypes that target cells have, tt those of target phenotypes that target
+    cells have and rr those of reference phenotypes that reference cells have: ``"percent"`` is rt / (rt + tt),
+    ``"homogeneous"`` rt / (tt + rr).  Returns ``(score, count)`` with count = target + reference cells; the score is
+    NaN when count < ``cell_count_thresh``, when a population is absent, or when one population outnumbers the other
+    by more than ``ratio_threshold`` (tested in this order).  ValueError for a phenotype in both populations and for
+    an unknown ``mixing_type``.  ``fov_neighbors_mat`` is left as it is."""
+    verify_in_list(provided_column_names=[cell_col, fov_col, label_col],
+                   cell_neighbors_columns=fov_neighbors_mat.columns)
+    _check_populations(target_cells, reference_cells, mixing_type)
+    types = fov_neighbors_mat[cell_col]
+    is_target, is_reference = types.isin(target_cells).to_numpy(), types.isin(reference_cells).to_numpy()
+    present = set(types.unique())
+    numeric = fov_neighbors_mat.drop(columns=[fov_col, label_col, cell_col])
+
+    def interactions(rows, cells):
+        # one column per listed phenotype that the FOV holds, in the list's order (a name listed twice counts twice)
+        cols = [c for c in cells if c in present]
+        return np.float64(sum(numeric.loc[rows, c].sum() for c in cols)) if cols else np.float64(0)
+    target_total, ref_total = int(is_target.sum()), int(is_reference.sum())
+    if _mixing_exit(target_total, ref_total, ratio_threshold, cell_count_thresh):
+        return np.nan, target_total + ref_total
+    score = _mixing_quotient(interactions(is_target, reference_cells), interactions(is_target, target_cells),
+                             interactions(is_reference, reference_cells), mixing_type)
+    return score, target_total + ref_total
+
+
+def compute_mixing_scores(cell_table, target_cells, reference_cells, mixing_type, distlim=50, ratio_threshold=5,
+                          cell_count_thresh=200, self_neighbor=False, included_fovs=None, fov_col=_FOV_ID,
+                          cell_type_col=_CELL_TYPE, centroid_cols=_CENTROIDS):
+    """The mixing score of every FOV of a cohort, straight from the cell table.
+
+    Equal, value for value (NaN included), to the notebook's loop -- ``create_neighborhood_matrix(cell_table,
+    distlim=distlim, self_neighbor=self_neighbor)``, then ``compute_mixing_score`` on every FOV's rows -- without the
+    distance files and without the neighbourhood matrix: target is bit 0 and reference bit 1 of a cell's mask, and one
+    pxsom_close_pair_counts launch gives, per FOV, the 2 x 2 table of close pairs between the two
+    populations; rt, tt and rr of ``compute_mixing_score`` are its entries [0, 1], [0, 0] and [1, 1], integers below
+    2^53, so the quotient is the loop's exactly.  The loop counts a population over the rows of the neighbourhood
+    matrix, which has dropped the cells without any neighbour; which cells those are comes from one
+    pxsom_neighbor_counts launch with a single type.  The totals and the three exits are evaluated per FOV on the host.
+    A phenotype listed twice in a population counts once.
+
+    Returns a frame with columns ``fov``, ``mixing_score`` and ``cell_count``, one row per FOV of ``included_fovs``
+    (default: every FOV, in order of first appearance)."""
+    _check_populations(target_cells, reference_cells, mixing_type)
+    if included_fovs is None:
+        included_fovs = cell_table[fov_col].unique()
+    included_fovs = list(included_fovs)
+    verify_in_list(fov_names=included_fovs, unique_fovs=cell_table[fov_col].unique())
+    missing = [c for c in centroid_cols if c not in cell_table.columns]
+    if len(centroid_cols) != 2 or missing:
+        raise ValueError("compute_mixing_scores needs two centroid columns in cell_table; missing: %s (pass "
+                         "centroid_cols=... if they are named differently)" % (missing or list(centroid_cols)))
+    types = cell_table[cell_type_col]
+    if types.isna().any():
+        raise ValueError("compute_mixing_scores: column %r holds missing values" % cell_type_col)
+
+    # rows of the included FOVs, FOV by FOV in the order of included_fovs: one segment each
+    fov_codes = pd.Categorical(cell_table[fov_col].to_numpy(), categories=pd.unique(np.asarray(included_fovs, dtype=object)))
+    codes = np.asarray(fov_codes.codes, dtype=np.int64)
+    n_fovs = len(fov_codes.categories)
+    rows = np.flatnonzero(codes >= 0)
+    rows = rows[np.argsort(codes[rows], kind="stable")]
+    seg = np.concatenate([[0], np.cumsum(np.bincount(codes[rows], minlength=n_fovs))]).astype(np.int64)
+    is_target, is_reference = types.isin(target_cells).to_numpy()[rows], types.isin(reference_cells).to_numpy()[rows]
+
+    pairs = np.zeros((n_fovs, 2, 2), dtype=np.int64)
+    target_total = reference_total = np.zeros(n_fovs, dtype=np.int64)
+    if len(rows):
+        xy = cell_table[list(centroid_cols)].to_numpy(dtype=np.float64)[rows]
+        member = is_target.astype(np.uint64) | (is_reference.astype(np.uint64) << np.uint64(1))
+        pairs = spatial_analysis_utils._close_pair_counts_device(xy, member, member, seg, 2, 2, distlim,
+                                                                 bool(self_neighbor))
+        kept = spatial_analysis_utils._neighbor_counts_device(xy, np.zeros(len(rows), dtype=np.int64), seg, 1, distlim,
+                                                              bool(self_neighbor))[:, 0] != 0
+        target_total = np.bincount(codes[rows][kept & is_target], minlength=n_fovs)
+        reference_total = np.bincount(codes[rows][kept & is_reference], minlength=n_fovs)
+
+    scores, counts = [], []
+    for f in range(n_fovs):
+        t, r = int(target_total[f]), int(reference_total[f])
+        counts.append(t + r)
+        scores.append(np.nan if _mixing_exit(t, r, ratio_threshold, cell_count_thresh) else
+                      _mixing_quotient(pairs[f, 0, 1], pairs[f, 0, 0], pairs[f, 1, 1], mixing_type))
+    position = {fov: f for f, fov in enumerate(fov_codes.categories)}
+    order = [position[fov] for fov in included_fovs]
+    return pd.DataFrame({"fov": included_fovs, "mixing_score": np.asarray(scores, dtype=np.float64)[order],
+                         "cell_count": np.asarray(counts, dtype=np.int64)[order]})

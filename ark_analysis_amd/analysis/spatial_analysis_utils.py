@@ -1,10 +1,14 @@
-"""Neighbour counts and k-means labels of the reference's ``ark.analysis.spatial_analysis_utils``.
+"""Neighbour counts, close-pair counts and k-means labels of the reference's ``ark.analysis.spatial_analysis_utils``.
 
 ``compute_neighbor_counts`` takes a FOV's centroids where the reference takes its distance matrix: the counts come from
-one pxsom_neighbor_counts launch and the N x N matrix is never built.  Not mirrored: ``calc_dist_matrix``
-and its ``.xr`` files (xarray is not a dependency here), the distance-feature columns
-(``append_distance_features_to_dataset``; the cell-distance analysis is ``cell_neighborhood_stats``), the enrichment statistics
-(``compute_close_cell_num``, ``calculate_enrichment_stats``) and everything that plots.
+one pxsom_neighbor_counts launch and the N x N matrix is never built.  ``compute_close_cell_num`` -- the
+primitive under the enrichment statistics -- does the same: the cells positive for each marker, or of each phenotype,
+are sets, a set is one bit of a 64-bit mask per cell, and the marker x marker table of close pairs is one
+pxsom_close_pair_counts launch (more than 64 sets go through blocks of 64 x 64).
+``get_pos_cell_labels_channel`` and ``get_pos_cell_labels_cluster`` are the reference's.  Not mirrored:
+``calc_dist_matrix`` and its ``.xr`` files (xarray is not a dependency here), the distance-feature columns
+(``append_distance_features_to_dataset``; the cell-distance analysis is ``cell_neighborhood_stats``), the bootstrap and
+z-scores over ``compute_close_cell_num`` (``calculate_enrichment_stats``) and everything that plots.
 
 ``compute_kmeans_inertia`` and ``compute_kmeans_silhouette`` are the reference's sweeps over k: by default the k-means fits
 stay on the host (as in ``generate_cluster_labels``), the silhouette scores of every k come from one pxsom_silhouette call
@@ -19,7 +23,10 @@ import warnings
 import numpy as np
 import pandas as pd
 
-_CELL_LABEL, _CELL_TYPE = "label", "cell_meta_cluster"
+from ..host_utils import verify_in_list
+
+_CELL_LABEL, _CELL_TYPE, _CELL_TYPE_NUM = "label", "cell_meta_cluster", "cell_meta_cluster_id"
+_MASK_BITS = 64         # sets per pxsom_close_pair_counts launch: a set is a bit of a uint64 mask
 
 
 # ---- device entry point (the CPU tests swap it for the numpy statement of the same contract) ------------------------
@@ -35,6 +42,22 @@ def _neighbor_counts_device(xy: np.ndarray, types: np.ndarray, seg: np.ndarray, 
         torch.from_numpy(np.ascontiguousarray(types, dtype=np.int32)).to(dev),
         torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int64)).to(dev), n_types, distlim, self_neighbor)
     return counts.cpu().numpy()
+
+
+def _close_pair_counts_device(xy: np.ndarray, member_q: np.ndarray, member_c: np.ndarray, seg: np.ndarray, n_sets_q: int,
+                              n_sets_c: int, distlim, self_neighbor: bool) -> np.ndarray:
+    """som_device.close_pair_counts on host arrays: ``xy`` [n, 2] float64, ``member_q`` / ``member_c`` [n] uint64 masks,
+    ``seg`` [F + 1] offsets -> [F, n_sets_q, n_sets_c] int64 on the host."""
+    import torch
+    from .. import _capi, som_device
+    dev = _capi.require_gpu()
+    as_i64 = lambda m: torch.from_numpy(np.ascontiguousarray(m, dtype=np.uint64).view(np.int64)).to(dev)  # noqa: E731
+    mq = as_i64(member_q)
+    mc = mq if member_c is member_q else as_i64(member_c)
+    out = som_device.close_pair_counts(
+        torch.from_numpy(np.ascontiguousarray(xy, dtype=np.float64)).to(dev), mq, mc,
+        torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int64)).to(dev), n_sets_q, n_sets_c, distlim, self_neighbor)
+    return out.cpu().numpy()
 
 
 def _silhouette_device(x: np.ndarray, labelings: np.ndarray, n_clusters) -> np.ndarray:
@@ -97,6 +120,94 @@ def compute_neighbor_counts(current_fov_neighborhood_data, centroids, distlim, s
     index = data.index.copy()
     return (pd.DataFrame(counts, columns=columns, index=index),
             pd.DataFrame(_freqs(counts), columns=columns, index=index.copy()))
+
+
+def _pack_sets(member: np.ndarray) -> np.ndarray:
+    """[n, S <= 64] bool -> [n] uint64 with bit s = column s."""
+    bits = np.uint64(1) << np.arange(member.shape[1], dtype=np.uint64)
+    return (member.astype(np.uint64) * bits).sum(axis=1, dtype=np.uint64)
+
+
+def set_pair_counts(xy, seg, member_q, member_c, distlim, self_neighbor=False):
+    """``[F, Sq, Sc]`` int64: per FOV (rows ``seg[f] .. seg[f + 1]``) and pair of sets, the ordered pairs (a, b) of
+    cells with ``member_q[a, s]`` and ``member_c[b, t]`` at float32 distance ``< distlim`` (and ``!= 0`` unless
+    ``self_neighbor``).  ``member_q`` [n, Sq] and ``member_c`` [n, Sc] are boolean; any number of sets: one
+    pxsom_close_pair_counts launch per block of 64 row sets x 64 column sets."""
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    member_q, member_c = np.asarray(member_q, dtype=bool), np.asarray(member_c, dtype=bool)
+    seg = np.asarray(seg, dtype=np.int64)
+    n = xy.shape[0]
+    if member_q.ndim != 2 or member_c.ndim != 2 or member_q.shape[0] != n or member_c.shape[0] != n:
+        raise ValueError("set_pair_counts: the memberships must be [n, sets] with one row per centroid (n = %d), got %s "
+                         "and %s" % (n, member_q.shape, member_c.shape))
+    out = np.zeros((len(seg) - 1, member_q.shape[1], member_c.shape[1]), dtype=np.int64)
+    same = member_c is member_q
+    packed_c = {}
+    for r in range(0, member_q.shape[1], _MASK_BITS):
+        mq = _pack_sets(member_q[:, r:r + _MASK_BITS])
+        for c in range(0, member_c.shape[1], _MASK_BITS):
+            if c not in packed_c:
+                packed_c[c] = mq if same and c == r else _pack_sets(member_c[:, c:c + _MASK_BITS])
+            nq, nc = min(_MASK_BITS, member_q.shape[1] - r), min(_MASK_BITS, member_c.shape[1] - c)
+            out[:, r:r + nq, c:c + nc] = _close_pair_counts_device(xy, mq, packed_c[c], seg, nq, nc, distlim,
+                                                                   bool(self_neighbor))
+    return out
+
+
+def get_pos_cell_labels_channel(thresh, current_fov_channel_data, cell_labels, current_marker):
+    """The labels (the entries of ``cell_labels``) of the cells whose ``current_marker`` column of
+    ``current_fov_channel_data`` lies above ``thresh``."""
+    return cell_labels[current_fov_channel_data[current_marker] > thresh]
+
+
+def get_pos_cell_labels_cluster(pheno, current_fov_neighborhood_data, cell_label_col, cell_type_col):
+    """The ``cell_label_col`` entries of the rows of ``current_fov_neighborhood_data`` whose ``cell_type_col`` equals
+    ``pheno``."""
+    data = current_fov_neighborhood_data
+    return data.loc[:, cell_label_col][data[cell_type_col] == pheno]
+
+
+def compute_close_cell_num(centroids, dist_lim, analysis_type, current_fov_data=None, current_fov_channel_data=None,
+                           cluster_ids=None, cell_types_analyze=None, thresh_vec=None, cell_label_col=_CELL_LABEL,
+                           cell_type_col=_CELL_TYPE_NUM, *, exact=False):
+    """Per pair (j, k) of markers (``analysis_type="channel"``: column j of ``current_fov_channel_data`` above
+    ``thresh_vec[j]``) or of phenotypes (``"cluster"``: ``cell_type_col == cluster_ids[j]``), how many ordered pairs of
+    distinct cells of one FOV -- the first positive for j, the second for k -- lie at float32 distance ``< dist_lim`` and
+    ``> 0``.
+
+    ``centroids`` is the ``[n, 2]`` array of the centroids of the rows of ``current_fov_data``, in the rows' order
+    (``current_fov_channel_data`` holds the same rows); the reference passes the FOV's distance matrix here and looks
+    the cells up by label.  The result is the reference's whenever labels are unique within the FOV.
+    ``cell_types_analyze`` is accepted and unused, as in the reference.
+
+    Returns ``(close_num, mark1_num, mark1poslabels)``: the table, the number of positive cells per marker and their
+    labels (a list of Series).  The reference sums into ``numpy.uint16``, so ``close_num`` is a uint16 array holding the
+    count modulo 65 536; ``exact=True`` returns the int64 counts themselves.
+    """
+    verify_in_list(analysis_type=analysis_type, good_analyses=["cluster", "channel"])
+    xy = np.asarray(centroids, dtype=np.float64).reshape(-1, 2)
+    if xy.shape[0] != len(current_fov_data):
+        raise ValueError("centroids must hold one (row, column) pair per row of the table: got %d for %d rows"
+                         % (xy.shape[0], len(current_fov_data)))
+    mark1poslabels, positive = [], []
+    if analysis_type == "channel":
+        if len(current_fov_channel_data) != len(current_fov_data):
+            raise ValueError("current_fov_channel_data must hold the rows of current_fov_data: got %d for %d rows"
+                             % (len(current_fov_channel_data), len(current_fov_data)))
+        cell_labels = current_fov_data[cell_label_col]
+        for j in range(len(thresh_vec)):
+            marker = current_fov_channel_data.columns[j]
+            mark1poslabels.append(get_pos_cell_labels_channel(thresh_vec[j], current_fov_channel_data, cell_labels,
+                                                              marker))
+            positive.append((current_fov_channel_data[marker] > thresh_vec[j]).to_numpy())
+    else:
+        for pheno in cluster_ids:
+            mark1poslabels.append(get_pos_cell_labels_cluster(pheno, current_fov_data, cell_label_col, cell_type_col))
+            positive.append((current_fov_data[cell_type_col] == pheno).to_numpy())
+    mark1_num = [len(labels) for labels in mark1poslabels]
+    member = np.stack(positive, axis=1) if positive else np.zeros((xy.shape[0], 0), dtype=bool)
+    counts = set_pair_counts(xy, [0, xy.shape[0]], member, member, dist_lim, False)[0]
+    return (counts if exact else counts.astype(np.uint16)), mark1_num, mark1poslabels
 
 
 _KMEANS_CHOICES = ("host", "device")

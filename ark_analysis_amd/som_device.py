@@ -1438,6 +1438,50 @@ def neighbor_counts(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_
     return counts
 
 
+CLOSE_PAIR_MAX_SETS = 64    # pxsom_close_pair_counts: a set is a bit of a 64-bit membership mask
+
+
+def close_pair_counts(xy: torch.Tensor, member_q: torch.Tensor, member_c: torch.Tensor, seg: torch.Tensor,
+                      n_sets_q: int, n_sets_c: int, distlim, self_neighbor: bool = False) -> torch.Tensor:
+    """pxsom_close_pair_counts: ``out[f, s, t]`` (``[F, n_sets_q, n_sets_c]`` int64, HBM) = the number of ordered pairs
+    (a, b) of cells of FOV f with bit s of ``member_q[a]`` and bit t of ``member_c[b]`` set and
+    ``float32(dist(a, b)) < distlim`` (and ``!= 0`` unless ``self_neighbor``: without it a cell pairs neither with itself
+    nor with a cell on its own centroid) -- the pair test of :func:`neighbor_counts`, the N x N matrix never built.
+    ``member_q`` / ``member_c`` are ``[n]`` int64 tensors holding the uint64 masks (bit 63 is the sign bit; they may be
+    the same tensor); bits at or above the set counts are ignored.  ``1 <= n_sets <= 64``: callers with more sets go
+    through blocks of 64 rows x 64 columns.  ``seg`` as for :func:`neighbor_counts`; the rows need no order inside a
+    FOV.  The entry clears the output itself."""
+    n_sets_q, n_sets_c = operator.index(n_sets_q), operator.index(n_sets_c)
+    if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float64 or not xy.is_cuda:
+        raise ValueError("xy must be an [n, 2] float64 HBM tensor")
+    n, dev = xy.shape[0], xy.device
+    for name, m in (("member_q", member_q), ("member_c", member_c)):
+        if m.dim() != 1 or m.shape[0] != n or m.dtype != torch.int64 or m.device != dev:
+            raise ValueError("%s must be an [n] int64 HBM vector (the bits of a uint64 mask) on xy's device" % name)
+    if seg.dim() != 1 or seg.numel() < 1 or seg.dtype != torch.int64 or seg.device != dev:
+        raise ValueError("seg must be an [F + 1] int64 HBM vector on xy's device")
+    if not (1 <= n_sets_q <= CLOSE_PAIR_MAX_SETS and 1 <= n_sets_c <= CLOSE_PAIR_MAX_SETS):
+        raise ValueError("n_sets_q and n_sets_c must lie in 1 .. %d, got %d and %d"
+                         % (CLOSE_PAIR_MAX_SETS, n_sets_q, n_sets_c))
+    seg = seg.contiguous()
+    n_fovs = seg.numel() - 1
+    ok = torch.stack([seg[0] == 0, seg[-1] == n, (seg[1:] >= seg[:-1]).all()]).cpu()
+    if not bool(ok.all()):
+        raise ValueError("seg must be non-decreasing offsets from 0 to n")
+    s_lim, s_zero = neighbor_thresholds(distlim)
+    out = torch.empty((n_fovs, n_sets_q, n_sets_c), dtype=torch.int64, device=dev)
+    if n_fovs == 0:
+        return out
+    xy, same = xy.contiguous(), member_c is member_q
+    member_q = member_q.contiguous()
+    member_c = member_q if same else member_c.contiguous()
+    rc = _capi.lib().pxsom_close_pair_counts(xy.data_ptr(), member_q.data_ptr(), member_c.data_ptr(), seg.data_ptr(),
+                                             n_fovs, n, n_sets_q, n_sets_c, s_lim, s_zero, 1 if self_neighbor else 0,
+                                             out.data_ptr(), _capi.stream_ptr())
+    _capi.check(rc, "pxsom_close_pair_counts")
+    return out
+
+
 # ---- cell-distance analysis (K14) -----------------------------------------------------------------------------------
 NEAREST_MAX_K = 32      # pxsom_nearest_type_means keeps the k smallest squared distances in registers
 _S_ZERO = None

@@ -642,6 +642,31 @@ int pxsom_neighbor_counts(const double *xy_dev, const int32_t *type_dev, const i
                           int64_t n, int n_types, double s_lim, double s_zero, int self_neighbor, int32_t *counts_dev,
                           void *stream);
 
+/* ---- close-pair counts between cell sets, per FOV, from the centroids (K20) -------------------------------------------
+ * reference: ark/analysis/spatial_analysis_utils.py compute_close_cell_num (the float32 distance matrix binarised with
+ * < dist_lim and > 0, subset to the rows positive for marker or phenotype j and the columns positive for k, summed) and
+ * the target / reference interaction totals of ark/analysis/neighborhood_analysis.py compute_mixing_score.  One
+ * stream-ordered launch covers the cohort; neither the N x N matrix nor an N x sets table is built.  Symbol added under
+ * ABI 9, none changed.
+ *   xy_dev        [n, 2] binary64 centroids, 16-byte aligned; n < 2^31
+ *   member_q_dev  [n] uint64: bit s says that the cell, as the first of a pair, is in row set s
+ *   member_c_dev  [n] uint64: bit t says that the cell, as the second of a pair, is in column set t (the two pointers
+ *                 may be equal).  Bits at or above n_sets_q / n_sets_c are ignored.
+ *   seg_dev       [n_fovs + 1] int64 offsets as for pxsom_neighbor_counts (clamped to [0, n] on the device; an empty FOV
+ *                 is allowed); the rows need no order inside a FOV
+ *   n_sets_q, n_sets_c   1 .. 64
+ *   s_lim, s_zero, self_neighbor   the pair test of pxsom_neighbor_counts: cells a and b of one FOV (b = a included)
+ *                 count when s = fl(fl(dx * dx) + fl(dy * dy)) < s_lim and (self_neighbor or s > s_zero)
+ * out_dev [n_fovs, n_sets_q, n_sets_c] int64: out[f, s, t] = the number of ordered pairs (a, b) of FOV f that count with
+ * bit s of member_q[a] and bit t of member_c[b] set.  The entry clears out_dev itself (one memset on the stream before
+ * the launch): the caller need not.  Integer additions only: the result does not depend on the grid and is the same
+ * on every run.  No workspace.  Every index into out_dev is built from f < n_fovs, s < n_sets_q, t < n_sets_c, so bad
+ * device-side input gives wrong counts, never a store outside out_dev.  Bad sizes, set counts, flag, NaN thresholds or
+ * null / misaligned pointers: PXSOM_ERR_INVALID_ARG before any HIP call. */
+int pxsom_close_pair_counts(const double *xy_dev, const uint64_t *member_q_dev, const uint64_t *member_c_dev,
+                            const int64_t *seg_dev, int64_t n_fovs, int64_t n, int n_sets_q, int n_sets_c, double s_lim,
+                            double s_zero, int self_neighbor, int64_t *out_dev, void *stream);
+
 /* ---- cell-distance analysis: per cell, the mean distance to its k nearest cells of every phenotype (K14) -------------
  * reference: ark/analysis/cell_neighborhood_stats.py calculate_mean_distance_to_cell_type over calc_dist_matrix's float32
  * matrix (the columns of one phenotype, where(dist > 0), np.sort per row, [:, :k].mean(axis=1)).  One stream-ordered
