@@ -18,6 +18,7 @@ import numpy as np
 import pandas as pd
 
 from ..host_utils import validate_paths, verify_in_list
+from ._cells import _to_device, centroid_columns, fov_rows_and_segments
 
 # the reference's column names (ark.settings)
 _FOV_ID, _CELL_LABEL, _CELL_TYPE = "fov", "label", "cell_meta_cluster"
@@ -29,14 +30,9 @@ MAX_K = 32      # som_device.NEAREST_MAX_K
 def _nearest_type_means_device(xy: np.ndarray, types: np.ndarray, seg: np.ndarray, n_types: int, k: int) -> np.ndarray:
     """som_device.nearest_type_means on host arrays: ``xy`` [n, 2] float64, ``types`` [n] in [0, n_types), ``seg``
     [F + 1] offsets -> [n, n_types] float32 on the host."""
-    import torch
-    from .. import _capi, som_device
-    dev = _capi.require_gpu()
-    means = som_device.nearest_type_means(
-        torch.from_numpy(np.ascontiguousarray(xy, dtype=np.float64)).to(dev),
-        torch.from_numpy(np.ascontiguousarray(types, dtype=np.int32)).to(dev),
-        torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int64)).to(dev), n_types, k)
-    return means.cpu().numpy()
+    from .. import som_device
+    xy, types, seg = _to_device(xy, np.float64), _to_device(types, np.int32), _to_device(seg, np.int64)
+    return som_device.nearest_type_means(xy, types, seg, n_types, k).cpu().numpy()
 
 
 def _check_k(k) -> int:
@@ -48,11 +44,7 @@ def _check_k(k) -> int:
 
 
 def _centroids(cell_table, centroid_cols, who):
-    missing = [c for c in centroid_cols if c not in cell_table.columns]
-    if len(centroid_cols) != 2 or missing:
-        raise ValueError("%s needs two centroid columns in cell_table; missing: %s (pass centroid_cols=... if they are "
-                         "named differently)" % (who, missing or list(centroid_cols)))
-    return cell_table[list(centroid_cols)].to_numpy(dtype=np.float64)
+    return cell_table[centroid_columns(cell_table, centroid_cols, who)].to_numpy(dtype=np.float64)
 
 
 def _type_codes(cell_table, cell_type_col, who):
@@ -123,8 +115,7 @@ def generate_cell_distance_analysis(cell_table, dist_mat_dir, save_path, k, cell
     fov_codes, fov_names = pd.factorize(cell_table[fov_col].to_numpy(), sort=True)      # np.unique order
     if (fov_codes < 0).any():
         raise ValueError("%s: column %r holds missing values" % (who, fov_col))
-    rows = np.argsort(fov_codes, kind="stable")
-    seg = np.concatenate([[0], np.cumsum(np.bincount(fov_codes, minlength=len(fov_names)))])
+    rows, seg = fov_rows_and_segments(fov_codes, len(fov_names))
 
     n_types = max(len(names), 1)
     means = np.empty((0, n_types), dtype=np.float32)

@@ -26,6 +26,7 @@ import pandas as pd
 
 from ..host_utils import verify_in_list
 from . import spatial_analysis_utils
+from ._cells import centroid_columns, fov_rows_and_segments
 
 # the reference's column names (ark.settings)
 _FOV_ID, _CELL_LABEL, _CELL_TYPE, _KMEANS_CLUSTER = "fov", "label", "cell_meta_cluster", "kmeans_neighborhood"
@@ -56,10 +57,7 @@ def create_neighborhood_matrix(all_data, dist_mat_dir=None, included_fovs=None, 
     if included_fovs is None:
         included_fovs = all_data[fov_col].unique()
     verify_in_list(fov_names=included_fovs, unique_fovs=all_data[fov_col].unique())
-    missing = [c for c in centroid_cols if c not in all_data.columns]
-    if len(centroid_cols) != 2 or missing:
-        raise ValueError("create_neighborhood_matrix needs two centroid columns in all_data; missing: %s (pass "
-                         "centroid_cols=... if they are named differently)" % (missing or list(centroid_cols)))
+    centroid_cols = centroid_columns(all_data, centroid_cols, "create_neighborhood_matrix", "all_data")
 
     id_cols = [fov_col, cell_label_col, cell_type_col]
     ids = all_data[id_cols].reset_index(drop=True)
@@ -71,14 +69,12 @@ def create_neighborhood_matrix(all_data, dist_mat_dir=None, included_fovs=None, 
     # rows of the included FOVs, FOV by FOV in table order: one segment each
     fov_codes, fov_names = pd.factorize(ids[fov_col].to_numpy(), sort=False)
     wanted = np.isin(fov_codes, np.flatnonzero(pd.Index(fov_names).isin(list(included_fovs))))
-    rows = np.flatnonzero(wanted)
-    rows = rows[np.argsort(fov_codes[rows], kind="stable")]
-    seg = np.concatenate([[0], np.cumsum(np.bincount(fov_codes[rows], minlength=len(fov_names)))])
+    rows, seg = fov_rows_and_segments(np.where(wanted, fov_codes, -1), len(fov_names))
 
     counts = np.zeros((n_cells, n_types))
     freqs = np.zeros((n_cells, n_types))
     if len(rows):
-        xy = all_data[list(centroid_cols)].to_numpy(dtype=np.float64)[rows]
+        xy = all_data[centroid_cols].to_numpy(dtype=np.float64)[rows]
         got = spatial_analysis_utils._neighbor_counts_device(xy, type_codes[rows], seg, n_types, distlim,
                                                              bool(self_neighbor)).astype(np.float64)
         counts[rows] = got
@@ -275,10 +271,7 @@ def compute_mixing_scores(cell_table, target_cells, reference_cells, mixing_type
         included_fovs = cell_table[fov_col].unique()
     included_fovs = list(included_fovs)
     verify_in_list(fov_names=included_fovs, unique_fovs=cell_table[fov_col].unique())
-    missing = [c for c in centroid_cols if c not in cell_table.columns]
-    if len(centroid_cols) != 2 or missing:
-        raise ValueError("compute_mixing_scores needs two centroid columns in cell_table; missing: %s (pass "
-                         "centroid_cols=... if they are named differently)" % (missing or list(centroid_cols)))
+    centroid_cols = centroid_columns(cell_table, centroid_cols, "compute_mixing_scores")
     types = cell_table[cell_type_col]
     if types.isna().any():
         raise ValueError("compute_mixing_scores: column %r holds missing values" % cell_type_col)
@@ -287,15 +280,13 @@ def compute_mixing_scores(cell_table, target_cells, reference_cells, mixing_type
     fov_codes = pd.Categorical(cell_table[fov_col].to_numpy(), categories=pd.unique(np.asarray(included_fovs, dtype=object)))
     codes = np.asarray(fov_codes.codes, dtype=np.int64)
     n_fovs = len(fov_codes.categories)
-    rows = np.flatnonzero(codes >= 0)
-    rows = rows[np.argsort(codes[rows], kind="stable")]
-    seg = np.concatenate([[0], np.cumsum(np.bincount(codes[rows], minlength=n_fovs))]).astype(np.int64)
+    rows, seg = fov_rows_and_segments(codes, n_fovs)
     is_target, is_reference = types.isin(target_cells).to_numpy()[rows], types.isin(reference_cells).to_numpy()[rows]
 
     pairs = np.zeros((n_fovs, 2, 2), dtype=np.int64)
     target_total = reference_total = np.zeros(n_fovs, dtype=np.int64)
     if len(rows):
-        xy = cell_table[list(centroid_cols)].to_numpy(dtype=np.float64)[rows]
+        xy = cell_table[centroid_cols].to_numpy(dtype=np.float64)[rows]
         member = is_target.astype(np.uint64) | (is_reference.astype(np.uint64) << np.uint64(1))
         pairs = spatial_analysis_utils._close_pair_counts_device(xy, member, member, seg, 2, 2, distlim,
                                                                  bool(self_neighbor))

@@ -24,6 +24,7 @@ import numpy as np
 import pandas as pd
 
 from ..host_utils import verify_in_list
+from ._cells import _to_device
 
 _CELL_LABEL, _CELL_TYPE, _CELL_TYPE_NUM = "label", "cell_meta_cluster", "cell_meta_cluster_id"
 _MASK_BITS = 64         # sets per pxsom_close_pair_counts launch: a set is a bit of a uint64 mask
@@ -34,30 +35,21 @@ def _neighbor_counts_device(xy: np.ndarray, types: np.ndarray, seg: np.ndarray, 
                             self_neighbor: bool) -> np.ndarray:
     """som_device.neighbor_counts on host arrays: ``xy`` [n, 2] float64, ``types`` [n] in [0, n_types), ``seg`` [F + 1]
     offsets -> [n, n_types] int32 on the host."""
-    import torch
-    from .. import _capi, som_device
-    dev = _capi.require_gpu()
-    counts = som_device.neighbor_counts(
-        torch.from_numpy(np.ascontiguousarray(xy, dtype=np.float64)).to(dev),
-        torch.from_numpy(np.ascontiguousarray(types, dtype=np.int32)).to(dev),
-        torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int64)).to(dev), n_types, distlim, self_neighbor)
-    return counts.cpu().numpy()
+    from .. import som_device
+    xy, types, seg = _to_device(xy, np.float64), _to_device(types, np.int32), _to_device(seg, np.int64)
+    return som_device.neighbor_counts(xy, types, seg, n_types, distlim, self_neighbor).cpu().numpy()
 
 
 def _close_pair_counts_device(xy: np.ndarray, member_q: np.ndarray, member_c: np.ndarray, seg: np.ndarray, n_sets_q: int,
                               n_sets_c: int, distlim, self_neighbor: bool) -> np.ndarray:
     """som_device.close_pair_counts on host arrays: ``xy`` [n, 2] float64, ``member_q`` / ``member_c`` [n] uint64 masks,
     ``seg`` [F + 1] offsets -> [F, n_sets_q, n_sets_c] int64 on the host."""
-    import torch
-    from .. import _capi, som_device
-    dev = _capi.require_gpu()
-    as_i64 = lambda m: torch.from_numpy(np.ascontiguousarray(m, dtype=np.uint64).view(np.int64)).to(dev)  # noqa: E731
+    from .. import som_device
+    as_i64 = lambda m: _to_device(np.asarray(m, dtype=np.uint64).view(np.int64), np.int64)  # noqa: E731
     mq = as_i64(member_q)
     mc = mq if member_c is member_q else as_i64(member_c)
-    out = som_device.close_pair_counts(
-        torch.from_numpy(np.ascontiguousarray(xy, dtype=np.float64)).to(dev), mq, mc,
-        torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int64)).to(dev), n_sets_q, n_sets_c, distlim, self_neighbor)
-    return out.cpu().numpy()
+    xy, seg = _to_device(xy, np.float64), _to_device(seg, np.int64)
+    return som_device.close_pair_counts(xy, mq, mc, seg, n_sets_q, n_sets_c, distlim, self_neighbor).cpu().numpy()
 
 
 def _silhouette_device(x: np.ndarray, labelings: np.ndarray, n_clusters) -> np.ndarray:

@@ -9,9 +9,9 @@
 // the cast are monotone, so the k smallest distances are those of the k smallest s: the selection runs on s, and only the
 // k survivors of a (cell, type) pair see a square root.
 //
-// Shape.  The walk of pxsom_fovwalk.h, the run's counter joined by a sorted list.  The list is L binary64 registers
-// (L = 8, 16 or 32, the smallest that holds k), ascending, the k live entries at the TOP (a[L - k .. L - 1], +inf until
-// filled) over L - k entries pinned at -inf:
+// Shape.  walk_fov_runs of pxsom_fovwalk.h (its memory-safety argument is there), the run's counter joined by a sorted
+// list.  The list is L binary64 registers (L = 8, 16 or 32, the smallest that holds k), ascending, the k live entries at
+// the TOP (a[L - k .. L - 1], +inf until filled) over L - k entries pinned at -inf:
 // the k-th smallest so far is always a[L - 1], a static register, and one compare against it rejects the common
 // candidate.  An insertion is a[j] = max(a[j - 1], min(a[j], s)) for every j (the pinned entries stay -inf by the same
 // formula), all indices static: no scratch.  When the run ends the live entries are shifted to a[0 .. k - 1] by a

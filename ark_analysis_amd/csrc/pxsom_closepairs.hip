@@ -6,12 +6,11 @@
 // totals of ark/analysis/neighborhood_analysis.py compute_mixing_score.  A cell may sit in many sets at once, so a set is
 // a bit of a 64-bit membership mask.  For every FOV f
 //   out[f, s, t] = #{ordered pairs (a, b) of cells of f : bit s of member_q[a], bit t of member_c[b], the pair counts}
-// with K13's pair test: s2 = fl(fl(dx * dx) + fl(dy * dy)) in binary64 without contraction counts when s2 < s_lim and
-// (self_neighbor or s2 > s_zero).  Neither the N x N matrix nor an N x sets table is built.
+// with K13's pair test, pair_is_close of pxsom_fovwalk.h.  Neither the N x N matrix nor an N x sets table is built.
 //
-// Shape.  K13's walk (one thread one query cell, a workgroup of 256 owns 256 consecutive rows and walks, for every FOV
-// those rows touch, the FOV's cells as candidates in tiles of 256 staged in LDS, every lane reading the same candidate),
-// with the set arithmetic bit-sliced so that it stays out of the loop over candidates:
+// Shape.  for_each_fov of pxsom_fovwalk.h (one thread one query cell, a workgroup of 256 owns 256 consecutive rows and
+// visits every FOV those rows touch), the FOV's cells as candidates in tiles of 256 staged in LDS, every lane reading the
+// same candidate, with the set arithmetic bit-sliced so that it stays out of the loop over candidates:
 //   - at staging each wave transposes the masks of its 64 candidates with one ballot per column set: cplane[t] is the
 //     64-bit word that says which of the 64 candidates are in set t (bits at or above n_sets_c are never looked at);
 //   - the loop over 64 candidates only gathers the lane's 64 pair tests into a 64-bit word `close`;
@@ -23,8 +22,8 @@
 // Per-lane counters are 32-bit (at most the cells of a FOV; the entry refuses n >= 2^31), the sums over lanes and out are
 // 64-bit.  Integer additions only, so out does not depend on the grid or on the order of the atomics.
 //
-// Memory safety does not depend on the device-side inputs: FOV offsets are clamped to [0, n], every index into out is
-// built from f < n_fovs, s < n_sets_q and t < n_sets_c, and mask bits above the set counts select nothing.
+// Memory safety: the argument of pxsom_fovwalk.h for the cell arrays; every index into out is built from f < n_fovs,
+// s < n_sets_q and t < n_sets_c, and mask bits above the set counts select nothing.
 #include "pxsom_common.h"
 #include "pxsom_fovwalk.h"
 
@@ -32,18 +31,6 @@ namespace {
 
 constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxSets = 64;
-
-template <bool SELF>
-__device__ __forceinline__ uint32_t pair_counts(double xi, double yi, double2 cj, double s_lim, double s_zero)
-{
-    const double s = squared_distance(xi, yi, cj);
-    if constexpr (SELF) {
-        (void)s_zero;
-        return s < s_lim ? 1u : 0u;
-    } else {
-        return (s < s_lim && s > s_zero) ? 1u : 0u;
-    }
-}
 
 // NCAP: how many column-set counters a lane keeps (n_sets_c <= NCAP).  The counters go to LDS CB columns at a time.
 template <bool SELF, int NCAP>
@@ -64,38 +51,17 @@ __global__ __launch_bounds__(kBlock) void close_pair_counts_kernel(const double2
     __shared__ double2 cand[kBlock];
     __shared__ unsigned long long cplane[kWaves * kMaxSets];   // [wave of candidates][column set]
     __shared__ uint32_t qplane[kMaxSets * 8];                  // [row set][32 rows of the workgroup per word]
-    __shared__ uint32_t rows[kBlock * STRIDE];
+    __shared__ uint32_t sums[kBlock * STRIDE];
 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = tid / kWave;
-    const int64_t r0 = (int64_t)blockIdx.x * kBlock;
-    const int64_t r1 = r0 + kBlock < n ? r0 + kBlock : n;
-    const int64_t i = r0 + tid;
-    const bool has_row = i < n;
-    double xi = 0.0, yi = 0.0;
-    unsigned long long mq = 0ull;
-    if (has_row) {
-        const double2 q = xy[i];
-        xi = q.x;
-        yi = q.y;
-        mq = member_q[i];
-    }
+    const BlockRows rows = load_block_rows(xy, n);
+    const double xi = rows.xi, yi = rows.yi;
+    const unsigned long long mq = rows.has_row ? member_q[rows.i] : 0ull;
 
-    // the first FOV that ends beyond r0
-    int64_t lo = 0, hi = n_fovs;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (seg[mid + 1] > r0) hi = mid; else lo = mid + 1;
-    }
-
-    for (int64_t f = lo; f < n_fovs; ++f) {
-        const int64_t beg = clamp_i64(seg[f], 0, n);
-        const int64_t end = clamp_i64(seg[f + 1], beg, n);
-        if (beg >= r1) break;
-        if (end <= r0 || end == beg) continue;
-        const bool mine = has_row && i >= beg && i < end;
-
+    for_each_fov(seg, n_fovs, n, rows,
+                 [&](int64_t f, int64_t beg, int64_t end, bool mine) __attribute__((always_inline)) {
         uint32_t count[NCAP];
 #pragma unroll
         for (int t = 0; t < NCAP; ++t) count[t] = 0u;
@@ -122,9 +88,11 @@ __global__ __launch_bounds__(kBlock) void close_pair_counts_kernel(const double2
                 const double2 *cc = cand + w0;
                 uint32_t close_lo = 0u, close_hi = 0u;
 #pragma unroll
-                for (int k = 0; k < 32; ++k) close_lo |= pair_counts<SELF>(xi, yi, cc[k], s_lim, s_zero) << k;
+                for (int k = 0; k < 32; ++k)
+                    close_lo |= (uint32_t)pair_is_close<SELF>(xi, yi, cc[k], s_lim, s_zero) << k;
 #pragma unroll
-                for (int k = 0; k < 32; ++k) close_hi |= pair_counts<SELF>(xi, yi, cc[32 + k], s_lim, s_zero) << k;
+                for (int k = 0; k < 32; ++k)
+                    close_hi |= (uint32_t)pair_is_close<SELF>(xi, yi, cc[32 + k], s_lim, s_zero) << k;
                 const unsigned long long *pl = cplane + (w0 / kWave) * kMaxSets;
 #pragma unroll
                 for (int g = 0; g < NCAP; g += 8) {
@@ -158,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void close_pair_counts_kernel(const double2
             if (pass * CB < n_sets_c) {
                 if (pass > 0) __syncthreads();   // the pass before has been summed
 #pragma unroll
-                for (int j = 0; j < CB; ++j) rows[tid * STRIDE + j] = count[pass * CB + j];
+                for (int j = 0; j < CB; ++j) sums[tid * STRIDE + j] = count[pass * CB + j];
                 __syncthreads();
                 const int col = pass * CB + col0;
                 for (int s = wave; s < n_sets_q; s += kWaves) {
@@ -168,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void close_pair_counts_kernel(const double2
                         while (bits) {
                             const int a = __builtin_ctz(bits);
                             bits &= bits - 1u;
-                            sum += rows[(wi * 32 + a) * STRIDE + col0];
+                            sum += sums[(wi * 32 + a) * STRIDE + col0];
                         }
                     }
                     if (col < n_sets_c && sum != 0ull)
@@ -176,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void close_pair_counts_kernel(const double2
                 }
             }
         }
-    }
+    });
 }
 
 template <bool SELF, int NCAP>
@@ -199,9 +167,7 @@ PXSOM_EXPORT int pxsom_close_pair_counts(const double *xy_dev, const uint64_t *m
     if (n < 0 || n_fovs < 0) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: n=%lld, n_fovs=%lld", fn, (long long)n, (long long)n_fovs);
     if (n_sets_q < 1 || n_sets_q > kMaxSets || n_sets_c < 1 || n_sets_c > kMaxSets)
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: n_sets_q=%d, n_sets_c=%d outside 1 .. %d", fn, n_sets_q, n_sets_c, kMaxSets);
-    if (self_neighbor != 0 && self_neighbor != 1)
-        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: self_neighbor=%d is not 0 or 1", fn, self_neighbor);
-    if (s_lim != s_lim || s_zero != s_zero) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: a threshold is NaN", fn);
+    if (const int rc = check_pair_test(fn, self_neighbor, s_lim, s_zero)) return rc;
     if (n > 0x7fffffffLL) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: n=%lld too large", fn, (long long)n);
     if (n_fovs > (int64_t)1 << 40) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: n_fovs=%lld too large", fn, (long long)n_fovs);
     if (!seg_dev) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: null seg", fn);

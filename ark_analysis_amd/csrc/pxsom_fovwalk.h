@@ -1,16 +1,19 @@
-// pxsom_fovwalk.h -- the walk that the per-cell kernels over FOVs share (K13 neighbour counts, K14 nearest-cell means).
+// pxsom_fovwalk.h -- what the per-cell kernels over FOVs share: the pair test (K13 neighbour counts, K20 close-pair
+// counts), the walk over FOVs (K20) and the walk over the type runs of FOVs (K13, K14 nearest-cell means).
 //
-// One thread owns one query cell (coordinates in registers); a workgroup of 256 owns 256 consecutive rows and walks, for
-// every FOV those rows touch, all the FOV's cells as candidates in tiles of 256 staged in LDS.  Every lane reads the same
-// candidate (one 16-byte broadcast read, no bank conflict).  The caller hands the cells of a FOV sorted by type, so the
-// candidates of one type are one run: what a run gathers lives in the policy's registers and one value per run is stored
-// when the run ends.  Where runs begin is known per tile from one ballot per wave at staging time (a 64-bit mask per 64
-// candidates), so the loop over a run carries no type test.  The run boundaries are the same for every lane: no atomics,
-// no LDS counters, any number of types.  Each thread writes every column of its own row exactly once -- the fill value
-// between the runs it met, after the last one, and for a row no FOV holds -- so the caller need not clear the output.
+// One thread owns one query cell (coordinates in registers); a workgroup of 256 owns 256 consecutive rows and visits
+// every FOV those rows touch (for_each_fov), taking the FOV's cells as candidates in tiles of 256 staged in LDS.  Every
+// lane reads the same candidate (one 16-byte broadcast read, no bank conflict).  Memory safety does not depend on the
+// device-side inputs: for_each_fov (and the same loop in walk_fov_runs) clamps the FOV offsets to [0, n], so a body that
+// indexes the cell arrays inside [beg, end) stays inside them whatever seg holds.
 //
-// Memory safety does not depend on the device-side inputs: FOV offsets are clamped to [0, n], and a type outside
-// [0, n_types) or out of order is never stored (its row is then wrong, not its neighbours' memory).
+// walk_fov_runs (K13, K14).  The caller hands the cells of a FOV sorted by type, so the candidates of one type are one
+// run: what a run gathers lives in the policy's registers and one value per run is stored when the run ends.  Where runs
+// begin is known per tile from one ballot per wave at staging time (a 64-bit mask per 64 candidates), so the loop over a
+// run carries no type test.  The run boundaries are the same for every lane: no atomics, no LDS counters, any number of
+// types.  Each thread writes every column of its own row exactly once -- the fill value between the runs it met, after
+// the last one, and for a row no FOV holds -- so the caller need not clear the output.  A type outside [0, n_types) or
+// out of order is never stored (its row is then wrong, not its neighbours' memory).
 //
 // The walk counts, per run, the candidates that count for the policy P, which gives
 //   void begin_run()                a run opens: forget the last one
@@ -63,6 +66,63 @@ __device__ __forceinline__ double squared_distance(double xi, double yi, double2
     return px + py;
 }
 
+// The pair test: float32(sqrt(s)) < distlim and (SELF or != 0), with the thresholds of som_device.neighbor_thresholds
+template <bool SELF>
+__device__ __forceinline__ bool pair_is_close(double xi, double yi, double2 cj, double s_lim, double s_zero)
+{
+    const double s = squared_distance(xi, yi, cj);
+    if constexpr (SELF) {
+        (void)s_zero;
+        return s < s_lim;
+    } else {
+        return s < s_lim && s > s_zero;
+    }
+}
+
+// The workgroup's rows [r0, r1) and the thread's query cell, row i (coordinates 0 without a row)
+struct BlockRows {
+    int64_t r0, r1, i;
+    bool has_row;
+    double xi, yi;
+};
+
+__device__ __forceinline__ BlockRows load_block_rows(const double2 *__restrict__ xy, int64_t n)
+{
+    BlockRows b;
+    b.r0 = (int64_t)blockIdx.x * kBlock;
+    b.r1 = b.r0 + kBlock < n ? b.r0 + kBlock : n;
+    b.i = b.r0 + threadIdx.x;
+    b.has_row = b.i < n;
+    b.xi = b.yi = 0.0;
+    if (b.has_row) {
+        const double2 q = xy[b.i];
+        b.xi = q.x;
+        b.yi = q.y;
+    }
+    return b;
+}
+
+// body(f, beg, end, mine) for every FOV f holding one of the workgroup's rows: its cells are rows [beg, end), not empty,
+// inside [0, n]; `mine`: the thread's row is one of them.  All threads take the same trips: body may __syncthreads().
+template <typename Body>
+__device__ __forceinline__ void for_each_fov(const int64_t *__restrict__ seg, int64_t n_fovs, int64_t n,
+                                             const BlockRows &rows, Body body)
+{
+    // the first FOV that ends beyond r0
+    int64_t lo = 0, hi = n_fovs;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (seg[mid + 1] > rows.r0) hi = mid; else lo = mid + 1;
+    }
+    for (int64_t f = lo; f < n_fovs; ++f) {
+        const int64_t beg = clamp_i64(seg[f], 0, n);
+        const int64_t end = clamp_i64(seg[f + 1], beg, n);
+        if (beg >= rows.r1) break;
+        if (end <= rows.r0 || end == beg) continue;
+        body(f, beg, end, rows.has_row && rows.i >= beg && rows.i < end);
+    }
+}
+
 // cand, ctype, run_start: the calling kernel's LDS, [kBlock], [kBlock] and [kBlock / kWave]
 template <typename T, typename P>
 __device__ __forceinline__ void walk_fov_runs(const double2 *__restrict__ xy, const int32_t *__restrict__ type,
@@ -71,6 +131,8 @@ __device__ __forceinline__ void walk_fov_runs(const double2 *__restrict__ xy, co
                                               unsigned long long *run_start, P &run)
 {
     const int tid = threadIdx.x;
+    // load_block_rows and for_each_fov, written out: through them the compiler schedules K13's loop otherwise and the
+    // kernel measured 3 - 6 % slower; like this K13 and K14 are the code they were.  Keep them in step.
     const int64_t r0 = (int64_t)blockIdx.x * kBlock;
     const int64_t r1 = r0 + kBlock < n ? r0 + kBlock : n;
     const int64_t i = r0 + tid;
@@ -83,13 +145,11 @@ __device__ __forceinline__ void walk_fov_runs(const double2 *__restrict__ xy, co
     }
     RowWriter<T> out{has_row ? out_rows + i * n_types : nullptr, n_types, 0, has_row, fill};
 
-    // the first FOV that ends beyond r0
     int64_t lo = 0, hi = n_fovs;
     while (lo < hi) {
         const int64_t mid = lo + (hi - lo) / 2;
         if (seg[mid + 1] > r0) hi = mid; else lo = mid + 1;
     }
-
     for (int64_t f = lo; f < n_fovs; ++f) {
         const int64_t beg = clamp_i64(seg[f], 0, n);
         const int64_t end = clamp_i64(seg[f + 1], beg, n);
@@ -136,6 +196,15 @@ __device__ __forceinline__ void walk_fov_runs(const double2 *__restrict__ xy, co
         if (mine && cur >= 0) out.put(cur, run.end_run(c));
     }
     out.finish();
+}
+
+// The check the entries with the pair test share (K13, K20)
+[[maybe_unused]] int check_pair_test(const char *fn, int self_neighbor, double s_lim, double s_zero)
+{
+    if (self_neighbor != 0 && self_neighbor != 1)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: self_neighbor=%d is not 0 or 1", fn, self_neighbor);
+    if (s_lim != s_lim || s_zero != s_zero) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: a threshold is NaN", fn);
+    return PXSOM_OK;
 }
 
 // The argument checks the entries share, with the entry's `own` checks (a callable returning a status) in their place

@@ -6,28 +6,12 @@
 // and j is a neighbour of i when s < s_lim and (self_neighbor or s > s_zero).  The two thresholds are found on the host
 // (som_device.neighbor_thresholds) such that this is float32(sqrt(s)) < distlim and float32(sqrt(s)) != 0 exactly.
 //
-// Shape.  The walk of pxsom_fovwalk.h; what a run gathers is one count in one register.
+// Shape.  walk_fov_runs of pxsom_fovwalk.h (its memory-safety argument is there); what a run gathers is one count in one
+// register.
 #include "pxsom_common.h"
 #include "pxsom_fovwalk.h"
 
 namespace {
-
-template <bool SELF>
-__device__ __forceinline__ int is_neighbor(double xi, double yi, double2 cj, double s_lim, double s_zero)
-{
-#pragma clang fp contract(off)
-    const double dx = xi - cj.x;
-    const double dy = yi - cj.y;
-    const double px = dx * dx;
-    const double py = dy * dy;
-    const double s = px + py;
-    if constexpr (SELF) {
-        (void)s_zero;
-        return s < s_lim ? 1 : 0;
-    } else {
-        return (s < s_lim && s > s_zero) ? 1 : 0;
-    }
-}
 
 template <bool SELF>
 struct CountRun {
@@ -37,7 +21,7 @@ struct CountRun {
     __device__ __forceinline__ void candidates(double xi, double yi, const double2 *cand, int p, int q, int &c) const
     {
 #pragma unroll 8
-        for (int k = p; k < q; ++k) c += is_neighbor<SELF>(xi, yi, cand[k], s_lim, s_zero);
+        for (int k = p; k < q; ++k) c += pair_is_close<SELF>(xi, yi, cand[k], s_lim, s_zero) ? 1 : 0;
     }
     __device__ __forceinline__ int32_t end_run(int count) const { return count; }
 };
@@ -64,12 +48,8 @@ PXSOM_EXPORT int pxsom_neighbor_counts(const double *xy_dev, const int32_t *type
 {
     const char *fn = "pxsom_neighbor_counts";
     unsigned blocks;
-    const int rc = check_cell_args(fn, xy_dev, type_dev, seg_dev, n_fovs, n, n_types, counts_dev, &blocks, [&] {
-        if (self_neighbor != 0 && self_neighbor != 1)
-            return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: self_neighbor=%d is not 0 or 1", fn, self_neighbor);
-        if (s_lim != s_lim || s_zero != s_zero) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: a threshold is NaN", fn);
-        return (int)PXSOM_OK;
-    });
+    const int rc = check_cell_args(fn, xy_dev, type_dev, seg_dev, n_fovs, n, n_types, counts_dev, &blocks,
+                                   [&] { return check_pair_test(fn, self_neighbor, s_lim, s_zero); });
     if (rc != PXSOM_OK || blocks == 0) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const double2 *xy = reinterpret_cast<const double2 *>(xy_dev);

@@ -1385,26 +1385,36 @@ def neighbor_thresholds(distlim) -> Tuple[float, float]:
     return (0.0 if at_lim is None else as_double(at_lim)), as_double(above_zero - 1)
 
 
+def _cell_args(xy: torch.Tensor, seg: torch.Tensor, check_rows):
+    """The ``xy`` / ``seg`` checks of the cell-geometry calls, with the caller's checks of its per-row vectors
+    (``check_rows(n, device)``) in their place between the two: ``(n, device, seg made contiguous, n_fovs)``."""
+    if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float64 or not xy.is_cuda:
+        raise ValueError("xy must be an [n, 2] float64 HBM tensor")
+    check_rows(xy.shape[0], xy.device)
+    if seg.dim() != 1 or seg.numel() < 1 or seg.dtype != torch.int64 or seg.device != xy.device:
+        raise ValueError("seg must be an [F + 1] int64 HBM vector on xy's device")
+    return xy.shape[0], xy.device, seg.contiguous(), seg.numel() - 1
+
+
+def _check_offsets(seg: torch.Tensor, n: int, *more) -> list:
+    """ValueError unless ``seg`` is right.  A call's one read-back: it returns the values of the 0-d bools ``more``."""
+    ok = torch.stack([seg[0] == 0, seg[-1] == n, (seg[1:] >= seg[:-1]).all(), *more]).cpu()
+    if not bool(ok[:3].all()):
+        raise ValueError("seg must be non-decreasing offsets from 0 to n")
+    return ok[3:].tolist()
+
+
 def _cells_sorted_by_type(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor, n_types: int):
     """The arguments :func:`neighbor_counts` and :func:`nearest_type_means` share, checked (one read-back), and the cells
     as their kernels want them: sorted by type inside each FOV.  Returns ``(xy_s, types_s, seg, order, n_fovs)``; sorted
     row r is the caller's row ``order[r]``.  With no cells the first two and ``order`` are None."""
-    if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float64 or not xy.is_cuda:
-        raise ValueError("xy must be an [n, 2] float64 HBM tensor")
-    n, dev = xy.shape[0], xy.device
-    if types.dim() != 1 or types.shape[0] != n or types.dtype not in (torch.int32, torch.int64) or types.device != dev:
-        raise ValueError("types must be an [n] int32 / int64 HBM vector on xy's device")
-    if seg.dim() != 1 or seg.numel() < 1 or seg.dtype != torch.int64 or seg.device != dev:
-        raise ValueError("seg must be an [F + 1] int64 HBM vector on xy's device")
+    def check_types(n, dev):
+        if types.dim() != 1 or types.shape[0] != n or types.dtype not in (torch.int32, torch.int64) or types.device != dev:
+            raise ValueError("types must be an [n] int32 / int64 HBM vector on xy's device")
+    n, dev, seg, n_fovs = _cell_args(xy, seg, check_types)
     if n_types < 1:
         raise ValueError("n_types must be at least 1")
-    seg = seg.contiguous()
-    n_fovs = seg.numel() - 1
-    ok = torch.stack([seg[0] == 0, seg[-1] == n, (seg[1:] >= seg[:-1]).all(),
-                      ((types >= 0) & (types < n_types)).all()]).cpu()
-    if not bool(ok[:3].all()):
-        raise ValueError("seg must be non-decreasing offsets from 0 to n")
-    if not bool(ok[3]):
+    if not _check_offsets(seg, n, ((types >= 0) & (types < n_types)).all())[0]:
         raise ValueError("types must lie in [0, n_types)")
     if n == 0:
         return None, None, seg, None, n_fovs
@@ -1452,22 +1462,15 @@ def close_pair_counts(xy: torch.Tensor, member_q: torch.Tensor, member_c: torch.
     through blocks of 64 rows x 64 columns.  ``seg`` as for :func:`neighbor_counts`; the rows need no order inside a
     FOV.  The entry clears the output itself."""
     n_sets_q, n_sets_c = operator.index(n_sets_q), operator.index(n_sets_c)
-    if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.float64 or not xy.is_cuda:
-        raise ValueError("xy must be an [n, 2] float64 HBM tensor")
-    n, dev = xy.shape[0], xy.device
-    for name, m in (("member_q", member_q), ("member_c", member_c)):
-        if m.dim() != 1 or m.shape[0] != n or m.dtype != torch.int64 or m.device != dev:
-            raise ValueError("%s must be an [n] int64 HBM vector (the bits of a uint64 mask) on xy's device" % name)
-    if seg.dim() != 1 or seg.numel() < 1 or seg.dtype != torch.int64 or seg.device != dev:
-        raise ValueError("seg must be an [F + 1] int64 HBM vector on xy's device")
+    def check_members(n, dev):
+        for name, m in (("member_q", member_q), ("member_c", member_c)):
+            if m.dim() != 1 or m.shape[0] != n or m.dtype != torch.int64 or m.device != dev:
+                raise ValueError("%s must be an [n] int64 HBM vector (the bits of a uint64 mask) on xy's device" % name)
+    n, dev, seg, n_fovs = _cell_args(xy, seg, check_members)
     if not (1 <= n_sets_q <= CLOSE_PAIR_MAX_SETS and 1 <= n_sets_c <= CLOSE_PAIR_MAX_SETS):
         raise ValueError("n_sets_q and n_sets_c must lie in 1 .. %d, got %d and %d"
                          % (CLOSE_PAIR_MAX_SETS, n_sets_q, n_sets_c))
-    seg = seg.contiguous()
-    n_fovs = seg.numel() - 1
-    ok = torch.stack([seg[0] == 0, seg[-1] == n, (seg[1:] >= seg[:-1]).all()]).cpu()
-    if not bool(ok.all()):
-        raise ValueError("seg must be non-decreasing offsets from 0 to n")
+    _check_offsets(seg, n)
     s_lim, s_zero = neighbor_thresholds(distlim)
     out = torch.empty((n_fovs, n_sets_q, n_sets_c), dtype=torch.int64, device=dev)
     if n_fovs == 0:

@@ -243,6 +243,39 @@ def test_error_paths(host_device):
         sau.compute_neighbor_counts(table, np.zeros((3, 2)), 50)
 
 
+def test_fov_rows_and_segments():
+    from ark_analysis_amd.analysis._cells import fov_rows_and_segments
+    # -1 entries are left out, a FOV's rows keep table order, FOVs 1 and 4 .. 5 (beyond the largest code) are empty
+    rows, seg = fov_rows_and_segments(np.array([2, -1, 0, 3, 2, -1, 0, 2]), 6)
+    assert rows.tolist() == [2, 6, 0, 4, 7, 3]
+    assert seg.tolist() == [0, 2, 2, 5, 6, 6, 6] and seg.dtype == np.int64
+    for codes in (np.full(4, -1), np.zeros(0, dtype=np.int64)):      # no wanted rows at all
+        rows, seg = fov_rows_and_segments(codes, 3)
+        assert rows.size == 0 and seg.tolist() == [0, 0, 0, 0] and seg.dtype == np.int64
+    rows, seg = fov_rows_and_segments(np.zeros(0, dtype=np.int64), 0)
+    assert rows.size == 0 and seg.tolist() == [0] and seg.dtype == np.int64
+    codes = np.random.RandomState(5).randint(-1, 7, size=500)
+    rows, seg = fov_rows_and_segments(codes, 9)
+    assert seg[-1] == (codes >= 0).sum() and seg.shape == (10,)
+    for f in range(9):
+        assert np.array_equal(rows[seg[f]:seg[f + 1]], np.flatnonzero(codes == f))      # ascending: table order
+
+
+@pytest.mark.parametrize("who,table_name", [("create_neighborhood_matrix", "all_data"),
+                                            ("compute_mixing_scores", "cell_table"),
+                                            ("generate_cell_distance_analysis", "cell_table")])
+def test_centroid_check_names_the_missing_column_in_each_caller_s_words(who, table_name):
+    from ark_analysis_amd.analysis._cells import centroid_columns
+    table = pd.DataFrame({"centroid-0": [1, 2], "cx": [3.5, 4.0]})
+    with pytest.raises(ValueError) as err:
+        centroid_columns(table, ("centroid-0", "centroid-1"), who, table_name)
+    assert str(err.value) == ("%s needs two centroid columns in %s; missing: ['centroid-1'] (pass centroid_cols=... if "
+                              "they are named differently)" % (who, table_name))
+    with pytest.raises(ValueError, match=r"%s needs two centroid columns in %s; missing: \['cx'\]" % (who, table_name)):
+        centroid_columns(table, ("cx",), who, table_name)      # not two columns: the ones given are named
+    assert centroid_columns(table, ("centroid-0", "cx"), who, table_name) == ["centroid-0", "cx"]
+
+
 def test_device_entry_point_is_loud_without_gpu():
     import torch
     if torch.cuda.is_available():
