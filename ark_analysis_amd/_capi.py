@@ -134,6 +134,15 @@ SYMBOLS = {
     "pxsom_pair_overlaps": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, ctypes.c_int32, ctypes.c_int32, _vp, _i64, _vp, _vp,
                                    _sz, _vp]),
     "pxsom_merge_apply": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "pxsom_nuclear_overlaps_workspace_bytes": (_sz, [_i64, _i64, ctypes.c_int32, ctypes.c_int32, _i64, ctypes.c_int32,
+                                                     ctypes.c_int32, _i32]),
+    "pxsom_nuclear_overlaps": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _i64, ctypes.c_int32,
+                                      ctypes.c_int32, _vp, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, _vp,
+                                      _sz, _i32, _vp]),
+    "pxsom_split_apply_workspace_bytes": (_sz, [_i64, ctypes.c_int32, ctypes.c_int32, _i64, ctypes.c_int32, ctypes.c_int32,
+                                                _i32]),
+    "pxsom_split_apply": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _i64, ctypes.c_int32, ctypes.c_int32,
+                                 _vp, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _i32, _vp]),
 }
 
 _lib = None

@@ -12,8 +12,10 @@ two transforms (``size_norm``, ``arcsinh``) and the frame layout stay on the hos
 one pxsom_region_shape and one pxsom_region_hull pass per compartment: raw integers from the device,
 the float columns from regionprops_extraction on the host; skimage is taken by its documented algorithms and parity
 with skimage itself is not pinned.  The bare call (``fast_extraction=False`` with none of the three lists named) keeps
-raising NotImplementedError, as do MIBItiff inputs, ``split_large_nuclei`` and a base property outside the eight built
-ones; ``create_marker_count_matrices`` / ``compute_marker_counts`` are not mirrored (they take and return xarray)."""
+raising NotImplementedError, as do MIBItiff inputs and a base property outside the eight built ones;
+``create_marker_count_matrices`` / ``compute_marker_counts`` are not mirrored (they take and return xarray).
+``split_large_nuclei=True`` re-cuts the nuclear plane at the cell borders on the device before anything nuclear is
+computed (segmentation_utils.split_large_nuclei); it needs ``nuclear_counts=True``."""
 import concurrent.futures
 import warnings
 
@@ -24,6 +26,7 @@ from .. import distributed, image_io
 from ..host_utils import list_folders, remove_file_extensions, verify_in_list
 from ..utils import data_utils
 from . import regionprops_extraction as rpe
+from . import segmentation_utils
 
 EXTRACTION_OPTIONS = ["positive_pixel", "center_weighting", "total_intensity"]   # signal_extraction.EXTRACTION_FUNCTION
 PRE_CHANNEL_COL, POST_CHANNEL_COL = "cell_size", "label"                          # ark.settings
@@ -161,9 +164,11 @@ def get_single_compartment_props(segmentation_labels, regionprops_base, regionpr
 
 
 def _fov_frames(fov, image_dev, channels, segs, mask_types, add_underscore, nuclear_counts, mode, threshold,
-                props=None):
+                props=None, split_nuclei=False):
     """The (size-normalised, arcsinh) frames of one FOV, one pair per mask type, from its segmentations ``segs``
-    (mask file suffix -> label plane).  ``props`` (base, single, multi, thresholds) adds the morphology columns."""
+    (mask file suffix -> label plane).  ``props`` (base, single, multi, thresholds) adds the morphology columns.  With
+    ``split_nuclei`` the nuclear plane of the whole_cell mask type is re-cut first (every cell label, ascending) and
+    everything nuclear -- the signal, the morphology and each cell's nucleus -- is computed from the re-cut plane."""
     tail = BASE_NAMES[1:] if props is None else rpe.table_names(props[0], props[1])
     frames = []
     for mask_type in mask_types:
@@ -176,6 +181,9 @@ def _fov_frames(fov, image_dev, channels, segs, mask_types, add_underscore, nucl
             verify_in_list(nuclear_label="nuclear", compartment_names=compartments)
         seg = segs[mask_suff]
         nuc = segs["_nuclear"] if nuclear_counts else None
+        if split_nuclei and nuc is not None and mask_type == "whole_cell":
+            cell_ids = np.unique(seg)
+            nuc = segmentation_utils.split_large_nuclei(seg, nuc, cell_ids[cell_ids != 0])
         q = _quantify(image_dev, seg, mode, threshold, nuc=nuc)
         if np.asarray(q["keys"]).size == 0:
             warnings.warn("No cells found in the following image: {}".format(fov))
@@ -250,8 +258,9 @@ def generate_cell_table(segmentation_dir, tiff_dir, img_sub_folder="TIFs", is_mi
     with ``centroid-0``, ``centroid-1`` at the end of the base block, the single-compartment properties and, with
     ``nuclear_counts`` in a FOV where some cell has a nucleus, ``nc_ratio``.  ``regionprops_kwargs`` may set
     ``small_concavity_minimum``, ``max_compactness`` and ``large_concavity_minimum``.  With ``fast_extraction=True`` the
-    lists are ignored.  Under a process group the FOVs are sharded over the ranks and every rank returns the whole
-    table."""
+    lists are ignored.  ``split_large_nuclei=True`` (with ``nuclear_counts=True``; NotImplementedError without) re-cuts
+    the nuclei at the cell borders first, as segmentation_utils.split_large_nuclei does.  Under a process group the FOVs
+    are sharded over the ranks and every rank returns the whole table."""
     if is_mibitiff:
         raise NotImplementedError("generate_cell_table: MIBItiff inputs are not implemented; "
                                   "use single-channel TIFFs (is_mibitiff=False)")
@@ -267,8 +276,10 @@ def generate_cell_table(segmentation_dir, tiff_dir, img_sub_folder="TIFs", is_mi
                                       "perimeter, convex area, concavities, nc_ratio, ...) are not implemented; "
                                       "fast_extraction=True is what runs")
         props = rpe.resolve_lists(*lists) + (rpe.concavity_thresholds(**kwargs.get("regionprops_kwargs", {})),)
-    if kwargs.get("split_large_nuclei", False):
-        raise NotImplementedError("generate_cell_table: split_large_nuclei=True is not implemented")
+    split_nuclei = bool(kwargs.get("split_large_nuclei", False))
+    if split_nuclei and not nuclear_counts:
+        raise NotImplementedError("generate_cell_table: split_large_nuclei=True needs nuclear_counts=True (without it "
+                                  "there is no nuclear plane to split; the reference ignores the flag then)")
     threshold = kwargs.get("signal_kwargs", {}).get("threshold", 0)
     fovs = sorted(fovs)
     suffixes = sorted({_mask_name(m, add_underscore)[1] for m in mask_types}
@@ -287,7 +298,7 @@ def generate_cell_table(segmentation_dir, tiff_dir, img_sub_folder="TIFs", is_mi
                 image_dev = _upload_image(image)
                 thr = _threshold_for(image.dtype, threshold)
                 done[fov] = _fov_frames(fov, image_dev, channels, segs, mask_types, add_underscore, nuclear_counts,
-                                        extraction, thr, props)
+                                        extraction, thr, props, split_nuclei)
     except Exception as e:      # noqa: BLE001 -- travels to every rank below, re-raised there
         error = e
     gathered = distributed.allgather_objects((error, done))

@@ -845,6 +845,55 @@ int pxsom_merge_apply(const int32_t *a_dev, int64_t lda, const int32_t *b_dev, i
                       const int32_t *winner_dev, const int32_t *removed_dev, int64_t table, int32_t *merged_dev, int64_t ldm,
                       int32_t *remaining_dev, int64_t ldr, void *stream);
 
+/* ---- K21: nuclei re-cut at cell borders (ark.segmentation.segmentation_utils.split_large_nuclei) ----------------------
+ * Two passes over a cell plane and a nuclear plane [h, w], each of its own label dtype (PXSOM_SEG_U8 .. PXSOM_SEG_I64) and
+ * row stride (ldc, ldn >= w elements); the choice between the passes is the host's, over per-cell tables.  A label names
+ * cell i (nucleus j) when it equals cell_keys_dev[i] (nuc_keys_dev[j]): int32 key tables, sorted ascending and unique,
+ * with their smallest and largest key (the K10 rule: a dense LUT in the workspace unless PXSOM_NUCSPLIT_FORCE_SEARCH, else
+ * a binary search; both routes give identical results).  0, a value no int32 holds and a label in neither table name
+ * nothing; whatever the planes hold, no label value is ever used as an index.
+ *
+ * pxsom_nuclear_overlaps:
+ *   area_dev [n_nuc] int64      the pixels of every nucleus in the whole plane
+ *   best_dev [n_cells, 2] int32 per cell the index of the nucleus with the most pixels inside the cell, the smaller index
+ *                               (label) on a tie, -1 for none, and that number of pixels (0 for none)
+ *   n_dev [2] int32             n_dev[1] = the RUNS of the image: stretches of one (cell label, nuclear label) pair, both
+ *                               non-zero, inside a row and inside an aligned group of 64 pixels of the flat raster order,
+ *                               which bounds the distinct (cell, nucleus) pairs; n_dev[0] = the distinct pairs of labels
+ *                               that are both in their table, or -1 -- and area_dev, best_dev untouched -- when the runs
+ *                               exceed capacity.
+ *   Called with area_dev == NULL and best_dev == NULL (capacity, workspace ignored) only the runs are counted:
+ *   n_dev = {0, runs}; a caller sizes the workspace from that and calls again.  The pair table has >= 2 * capacity slots
+ *   and takes at most one insertion per run, and none when runs > capacity: it cannot overflow.  No n_cells x n_nuc table,
+ *   no index planes, integer atomics only (the per-cell choice is a 64-bit maximum): the same input gives the same bytes
+ *   on every run.  Workspace: pxsom_nuclear_overlaps_workspace_bytes (0 for a capacity outside 1 .. 2^27).
+ *
+ * pxsom_split_apply: out_dev [h, w] of the nuclear plane's dtype, row stride ldo.  With c, j the indices of a pixel's cell
+ * and nucleus (-1: none):
+ *   out[p] = (c >= 0 && j >= 0 && chosen[c] == j && cell_value[c] >= 0) ? cell_value[c]
+ *          : (j >= 0 ? nuc_value[j] : nuc[p])
+ * chosen_dev [n_cells] int32, cell_value_dev [n_cells] int64 (-1: the cell splits nothing), nuc_value_dev [n_nuc] int64 (the
+ * label itself, or 0 for a remnant that is dropped); the values must fit the dtype.  Workspace:
+ * pxsom_split_apply_workspace_bytes (the LUTs; may be 0).
+ *
+ * Bad sizes (h * w <= 2^31 - 1), strides, dtype codes, flags, key counts, pointers, capacity or workspace:
+ * PXSOM_ERR_INVALID_ARG, the limit in the message, before any HIP call, for both entries. */
+#define PXSOM_NUCSPLIT_FORCE_SEARCH 1
+size_t pxsom_nuclear_overlaps_workspace_bytes(int64_t capacity, int64_t n_cells, int32_t cell_min, int32_t cell_max,
+                                              int64_t n_nuc, int32_t nuc_min, int32_t nuc_max, int flags);
+int pxsom_nuclear_overlaps(const void *cell_dev, int cell_dtype, int64_t ldc, const void *nuc_dev, int nuc_dtype, int64_t ldn,
+                           int h, int w, const int32_t *cell_keys_dev, int64_t n_cells, int32_t cell_min, int32_t cell_max,
+                           const int32_t *nuc_keys_dev, int64_t n_nuc, int32_t nuc_min, int32_t nuc_max, int64_t *area_dev,
+                           int32_t *best_dev, int64_t capacity, int32_t *n_dev, void *workspace_dev, size_t workspace_bytes,
+                           int flags, void *stream);
+size_t pxsom_split_apply_workspace_bytes(int64_t n_cells, int32_t cell_min, int32_t cell_max, int64_t n_nuc, int32_t nuc_min,
+                                         int32_t nuc_max, int flags);
+int pxsom_split_apply(const void *cell_dev, int cell_dtype, int64_t ldc, const void *nuc_dev, int nuc_dtype, int64_t ldn, int h,
+                      int w, const int32_t *cell_keys_dev, int64_t n_cells, int32_t cell_min, int32_t cell_max,
+                      const int32_t *nuc_keys_dev, int64_t n_nuc, int32_t nuc_min, int32_t nuc_max, const int32_t *chosen_dev,
+                      const int64_t *cell_value_dev, const int64_t *nuc_value_dev, void *out_dev, int64_t ldo,
+                      void *workspace_dev, size_t workspace_bytes, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
