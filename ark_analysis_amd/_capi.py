@@ -128,6 +128,7 @@ SYMBOLS = {
     "pxsom_components_select": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _i64, _vp]),
     "pxsom_gaussian_blur_plane_mode": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "pxsom_binarize_plane": (_i32, [_vp, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _i64, _vp]),
+    "pxsom_ridge_sign": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _f64, _vp, _i64, _vp]),
     "pxsom_label_regions_workspace_bytes": (_sz, [_i32, _i32]),
     "pxsom_label_regions": (_i32, [_vp, _i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
     "pxsom_pair_overlaps_workspace_bytes": (_sz, [_i64]),

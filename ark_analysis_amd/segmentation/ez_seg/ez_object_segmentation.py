@@ -6,7 +6,12 @@ pxsom_label_components and pxsom_components_select); paths, the TIFFs and the lo
 skimage's functions are taken by their documented semantics (``filters.gaussian`` = scipy's gaussian_filter with
 mode="nearest" and truncate 4 in float32 / float64, ``threshold_local``'s default Gaussian method,
 ``remove_small_holes`` with connectivity 1 and a strict <, ``measure.label(connectivity=2)``); parity with skimage itself
-is unpinned.  ``object_shape_type="projection"`` (the Meijering filter) is not implemented."""
+is unpinned.
+
+``object_shape_type="projection"`` puts ``filters.meijering(mask, sigmas=range(1, 5), black_ridges=False) > 0`` between the
+hole fill and the labelling.  That filter is this project's statement of skimage 0.19's algorithm (som_device.ridge_sign,
+DESIGN.md K22), unpinned against skimage, so it is opt-in: with ``PROJECTION_FILTER = None`` (the default) "projection"
+raises NotImplementedError as before; ``ez_object_segmentation.PROJECTION_FILTER = "meijering"`` enables it."""
 import os
 
 import numpy as np
@@ -16,7 +21,12 @@ from ...host_utils import validate_paths, verify_in_list
 from .ez_seg_utils import log_creator
 
 
-def _object_mask_device(img, sigma, thresh, hole_size, min_area, max_area, local_block=None) -> np.ndarray:
+# How "projection" objects are filtered: None (refused) or "meijering"; read at call time.
+PROJECTION_FILTER = None
+_MEIJERING = (range(1, 5, 1), 0.5)         # the reference's sigmas; skimage's alpha = 1 / ndim
+
+
+def _object_mask_device(img, sigma, thresh, hole_size, min_area, max_area, local_block=None, ridge=None) -> np.ndarray:
     """som_device.object_mask on a host image -> host int32 labels.  The one device entry point of the object masks (the
     CPU tests swap it for the numpy statement of the same contract)."""
     import torch
@@ -26,7 +36,7 @@ def _object_mask_device(img, sigma, thresh, hole_size, min_area, max_area, local
     if img.dtype not in (np.float32, np.float64):
         img = img.astype(np.float64)           # filters.gaussian(preserve_range=True): "image.astype(float)"
     t = torch.from_numpy(img if img.flags.writeable else img.copy()).to(dev)
-    return som_device.object_mask(t, sigma, thresh, hole_size, min_area, max_area, local_block).cpu().numpy()
+    return som_device.object_mask(t, sigma, thresh, hole_size, min_area, max_area, local_block, ridge=ridge).cpu().numpy()
 
 
 def check_blur_sigma(sigma) -> None:
@@ -64,6 +74,8 @@ def create_object_masks(image_data_dir, img_sub_folder, fov_list, mask_name, cha
 
     if rank == 0:
         logged = {key: settings[key] for key in _LOGGED}
+        if object_shape_type == "projection":
+            logged["projection_filter"] = PROJECTION_FILTER
         log_creator(logged, log_dir, mask_name + "_segmentation_log.txt")
     distributed.barrier()
     print("ez masks built and saved")
@@ -78,9 +90,15 @@ def _create_object_mask(input_image, object_shape_type="blob", sigma=1, thresh=N
     None (everything > 0).  ``hole_size``: background holes below this area are filled; "auto" takes
     ``get_block_size("small_holes", ...)``, None fills nothing."""
     verify_in_list(object_shape_type=[object_shape_type], object_shape_options=_SHAPES)
+    ridge = None
     if object_shape_type == "projection":
-        raise NotImplementedError("object_shape_type 'projection' (skimage's Meijering filter) is not implemented "
-                                  "on the device")
+        if PROJECTION_FILTER is None:
+            raise NotImplementedError("object_shape_type 'projection' (skimage's Meijering filter) is not implemented "
+                                      "on the device by default: set ez_object_segmentation.PROJECTION_FILTER = "
+                                      "'meijering' to take this project's statement of skimage 0.19's filter")
+        if PROJECTION_FILTER != "meijering":
+            raise ValueError("PROJECTION_FILTER must be None or 'meijering', got %r" % (PROJECTION_FILTER,))
+        ridge = _MEIJERING
     image = np.asarray(input_image if isinstance(input_image, np.ndarray) else input_image.to_numpy())
     if image.ndim != 2:
         raise ValueError("input_image must be a 2-D image, got shape %s" % (image.shape,))
@@ -106,7 +124,12 @@ def _create_object_mask(input_image, object_shape_type="blob", sigma=1, thresh=N
 
     if image.size == 0:
         return np.zeros(image.shape, dtype=np.int32)
-    return _object_mask_device(image, sigma, thresh, holes, min_object_area, max_object_area, local_block)
+    if ridge is None:
+        return _object_mask_device(image, sigma, thresh, holes, min_object_area, max_object_area, local_block)
+    if min(image.shape) < 2:                # np.gradient's refusal, in its words
+        raise ValueError("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements "
+                         "are required.")
+    return _object_mask_device(image, sigma, thresh, holes, min_object_area, max_object_area, local_block, ridge=ridge)
 
 
 def get_block_size(block_type, fov_dim, img_shape) -> int:

@@ -881,13 +881,48 @@ def binarize_plane(plane: torch.Tensor, mode: int = BIN_POSITIVE, level: float =
     return out
 
 
-def object_mask(img: torch.Tensor, sigma, thresh, hole_size, min_area, max_area, local_block=None) -> torch.Tensor:
+RIDGE_MAX_RADIUS, RIDGE_MAX_SCALES = 16, 8           # kRidgeMaxRadius / kRidgeMaxScales of csrc/pxsom_ridge.hip
+
+
+def ridge_sign(fg: torch.Tensor, sigmas=(1, 2, 3, 4), alpha=0.5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``skimage.filters.meijering(fg != 0, sigmas, alpha, black_ridges=False) > 0`` in skimage 0.19's statement
+    (include/pxsom.h "K22"; parity with skimage itself is unpinned) of a ``[H, W]`` uint8 / bool HBM plane (rows contiguous,
+    any row stride) -> uint8 ``[H, W]`` of 1 / 0 in HBM (``out`` if given: rows contiguous, any row stride, not ``fg``).
+    One launch of pxsom_ridge_sign.  ``H`` and ``W`` are at least 2, as np.gradient demands; up to 8 scales, each with
+    ``int(4 sigma + 0.5)`` between 1 and 16."""
+    fg = _binary_plane(fg, "fg")
+    h, w = fg.shape
+    if h < 2 or w < 2:
+        raise ValueError("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements "
+                         "are required.")
+    sigmas = list(sigmas)
+    if not 1 <= len(sigmas) <= RIDGE_MAX_SCALES:
+        raise ValueError("ridge_sign takes 1 to %d scales, got %d" % (RIDGE_MAX_SCALES, len(sigmas)))
+    if not all(float(s) > 0 and np.isfinite(float(s)) for s in sigmas) or not np.isfinite(float(alpha)):
+        raise ValueError("ridge_sign takes finite sigmas > 0 and a finite alpha, got %r and %r" % (sigmas, alpha))
+    kernels = [gaussian_kernel1d(float(s)) for s in sigmas]
+    for s, (_, radius) in zip(sigmas, kernels):
+        if not 1 <= radius <= RIDGE_MAX_RADIUS:
+            raise NotImplementedError("ridge_sign: sigma %r has radius %d outside [1, %d]" % (s, radius, RIDGE_MAX_RADIUS))
+    weights = np.ascontiguousarray(np.concatenate([k for k, _ in kernels]), dtype=np.float64)
+    radii = np.array([r for _, r in kernels], dtype=np.int32)
+    scales = np.array([float(s ** 2) for s in sigmas], dtype=np.float64)
+    out = _rows_plane(out, h, w, torch.uint8, fg.device, "out")
+    rc = _capi.lib().pxsom_ridge_sign(fg.data_ptr(), h, w, _ld(fg), weights.ctypes.data, radii.ctypes.data, scales.ctypes.data,
+                                      len(sigmas), float(alpha), out.data_ptr(), _ld(out), _capi.stream_ptr())
+    _capi.check(rc, "pxsom_ridge_sign")
+    return out
+
+
+def object_mask(img: torch.Tensor, sigma, thresh, hole_size, min_area, max_area, local_block=None, ridge=None) -> torch.Tensor:
     """The device chain of ``_create_object_mask`` on a ``[H, W]`` HBM image -> int32 ``[H, W]`` labels in HBM.
     float32 / float64 images go as they are, any other dtype is cast to float64 (skimage's ``preserve_range`` rule).
       blur       ``sigma`` None: none; else ``gaussian_filter(x, sigma, mode='nearest')`` in x's dtype
       threshold  ``thresh`` None: ``blur > 0``; an int: ``p = np.percentile(blur[blur != 0], thresh)``, foreground
                  ``!(blur < p) & blur > 0``; "auto": ``blur > gaussian_filter(blur, (local_block - 1) / 6, mode='reflect')``
       holes      ``hole_size`` None: none; else background components (4-neighbourhood) of area < hole_size are filled
+      ridge      ``ridge`` None: none; a ``(sigmas, alpha)`` tuple: the foreground becomes :func:`ridge_sign` of it
+                 ("projection" objects)
       labels     8-neighbourhood components, kept where ``min_area <= area <= max_area`` (not renumbered)
     The percentile is the one value read back to the host: pxsom_quantile_f32 / pxsom_quantile_nonzero with their
     ``!= 0`` keep rule (bits equal numpy's for both dtypes; a NaN pixel is dropped there where numpy's result turns NaN)."""
@@ -911,6 +946,8 @@ def object_mask(img: torch.Tensor, sigma, thresh, hole_size, min_area, max_area,
     if hole_size is not None:
         holes, _, hole_areas = label_components(fg, 1, invert=True)
         fg = components_select(holes, hole_areas, "fill", fg=fg, area_threshold=hole_size)
+    if ridge is not None:
+        fg = ridge_sign(fg, ridge[0], ridge[1])
     labels, _, areas = label_components(fg, 2)
     return components_select(labels, areas, "keep", min_area=min_area, max_area=max_area, out=labels)
 

@@ -801,6 +801,32 @@ int pxsom_gaussian_blur_plane_mode(const void *in_dev, void *out_dev, void *tmp_
 int pxsom_binarize_plane(const void *plane_dev, int dtype, int h, int w, int mode, double level, const void *local_dev,
                          uint8_t *out_dev, int64_t ldo, void *stream);
 
+/* ---- K22: the sign of the Meijering ridge filter on a binary plane ("projection" object masks) ------------------------
+ * reference: _create_object_mask(object_shape_type="projection"): skimage.filters.meijering(mask, sigmas=range(1, 5),
+ * black_ridges=False), of which only `> 0` is used.  skimage 0.19's filter is taken by its algorithm as restated below;
+ * parity with skimage itself is unpinned.  A symbol added under ABI 9, none changed.
+ *
+ * pxsom_ridge_sign: out = OR over the scales s of (aux_s < 0), where with x = (fg != 0) as binary64
+ *   g   = scipy.ndimage.gaussian_filter(x, sigma_s, mode="reflect", truncate=4): axis 0 first, then axis 1; each pass is
+ *         correlate1d's symmetric branch (tmp = in * w[0]; for d = r .. 1: tmp += (in[-d] + in[+d]) * w[d]), the line
+ *         extended by reflection however short it is
+ *   g0  = np.gradient(g, axis=0), g1 = np.gradient(g, axis=1): unit spacing, edge_order 1 -- (f[i+1] - f[i-1]) / 2.0 inside,
+ *         f[1] - f[0] and f[n-1] - f[n-2] at the two ends
+ *   Hrr = s2 * np.gradient(g0, axis=0), Hrc = s2 * np.gradient(g0, axis=1), Hcc = s2 * np.gradient(g1, axis=1)
+ *   d = Hrr - Hcc; r = sqrt(d*d + 4.0*(Hrc*Hrc)); t = Hrr + Hcc; e_hi = (t + r) / 2.0; e_lo = (t - r) / 2.0
+ *   (big, small) = |e_lo| >= |e_hi| ? (e_lo, e_hi) : (e_hi, e_lo);  aux = big + alpha * small
+ * in binary64 with one rounding per operation, no FMA contraction and a correctly rounded square root.
+ *   fg_dev        [h, w] uint8, row stride ld >= w; a pixel counts as 1 when != 0
+ *   weights_host  the 2 r + 1 weights of each scale's symmetric kernel, concatenated (host memory)
+ *   radii_host    [n_scales] the radius r of each scale;  scales_host [n_scales] the factor s2 (sigma squared)
+ *   out_dev       [h, w] uint8, row stride ldo >= w, every pixel written 1 or 0; must not overlap fg_dev
+ * One launch, no workspace.  PXSOM_ERR_INVALID_ARG before any HIP call: a null pointer, h < 2 or w < 2 (np.gradient's
+ * minimum), ld < w or ldo < w, n_scales outside 1 .. 8, a radius < 1, a factor that is not finite and > 0, a non-finite
+ * alpha, out overlapping fg.  PXSOM_ERR_UNSUPPORTED: a radius > 16 (sigma = 4 is the reference's largest), h * w beyond
+ * int32. */
+int pxsom_ridge_sign(const uint8_t *fg_dev, int h, int w, int64_t ld, const double *weights_host, const int *radii_host,
+                     const double *scales_host, int n_scales, double alpha, uint8_t *out_dev, int64_t ldo, void *stream);
+
 /* ---- merging ez_seg object masks into the cell segmentation (K18) -----------------------------------------------------
  * reference: ark/segmentation/ez_seg/merge_masks.py merge_masks_single (skimage.morphology.label of both masks, one
  * full-image logical_and per candidate cell of every object).  Symbols added under ABI 9, none changed.
