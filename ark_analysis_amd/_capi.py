@@ -181,6 +181,11 @@ def check(rc: int, what: str) -> None:
         raise PxsomError(f"{what}: {_STATUS.get(rc, rc)}: {msg.decode(errors='replace') if msg else ''}")
 
 
+def call(name: str, *args) -> None:
+    """The status-returning entry ``name`` with ``args``; PxsomError, named after the entry, unless it returns PXSOM_OK."""
+    check(getattr(lib(), name)(*args), name)
+
+
 def require_gpu() -> torch.device:
     """The product path is HIP-only: fail loudly when there is no GPU."""
     if not torch.cuda.is_available():

@@ -1,0 +1,477 @@
+"""Image planes and masks: cluster and segmentation masks, the plane blurs, object masks (K16, K22), mask merging (K18)."""
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import _capi
+from ._args import (PAIR_CAPACITY_MAX, PLANE_DTYPES, PLANE_MODE_DTYPES, SEG_DTYPES, SEG_F64, _binary_plane, _label_image,
+                    _label_pair, _label_plane, _ld, _like_plane, _rows_plane)
+from .pixels import gaussian_kernel1d, quantile_f32, quantile_nonzero
+
+
+MASK_BAD_LABEL, MASK_BAD_PIXEL = 1, 2   # include/pxsom.h PXSOM_MASK_*
+LUT_UNMAPPED = -2 ** 31                 # PXSOM_LUT_UNMAPPED
+
+
+def cluster_mask(row_index: torch.Tensor, column_index: torch.Tensor, labels: torch.Tensor, lut: torch.Tensor,
+                 h: int, w: int):
+    """``mask.ravel()[row_index * w + column_index] = lut[labels]`` on an int16 ``[h, w]`` image of zeros
+    (last row wins for a pixel listed twice).  int64 HBM vectors, int32 LUT.  Returns ``(mask, status)``:
+    status 0, or MASK_BAD_LABEL / MASK_BAD_PIXEL bits (synchronises to read it)."""
+    for name, t in (("row_index", row_index), ("column_index", column_index), ("labels", labels)):
+        if t.dtype != torch.int64 or not t.is_cuda or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64 HBM vector")
+    if not (row_index.numel() == column_index.numel() == labels.numel()):
+        raise ValueError("row_index, column_index and labels must have one entry per table row")
+    if lut.dtype != torch.int32 or not lut.is_cuda or not lut.is_contiguous():
+        raise ValueError("lut must be a contiguous int32 HBM vector")
+    dev = labels.device
+    mask = torch.empty((int(h), int(w)), dtype=torch.int16, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    wsb = _capi.lib().pxsom_cluster_mask_workspace_bytes(int(h), int(w))
+    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
+    _capi.call("pxsom_cluster_mask", row_index.data_ptr(), column_index.data_ptr(), labels.data_ptr(),
+               labels.numel(), lut.data_ptr(), lut.numel(), int(h), int(w),
+               mask.data_ptr(), status.data_ptr(), ws.data_ptr(), wsb, _capi.stream_ptr())
+    return mask, int(status.item())
+
+
+SEG_ERODE = {None: 0, "thick": 1, "inner": 2}
+SEGMASK_FORCE_SEARCH = 1
+
+
+def segmask_table(keys, values, device, float_values: bool = False):
+    """Host (key -> value) arrays as the device table of :func:`segmentation_mask`: ``keys`` int32, sorted ascending and
+    unique (checked here: the library relies on it), ``values`` int32, or float64 with ``float_values``."""
+    keys = np.ascontiguousarray(keys, dtype=np.int32)
+    values = np.ascontiguousarray(values, dtype=np.float64 if float_values else np.int32)
+    if keys.ndim != 1 or values.shape != keys.shape:
+        raise ValueError("keys and values must be vectors of one length")
+    if keys.size > 1 and not np.all(keys[1:] > keys[:-1]):
+        raise ValueError("keys must be sorted ascending without duplicates")
+    return (torch.from_numpy(keys).to(device), torch.from_numpy(values).to(device),
+            int(keys[0]) if keys.size else 0, int(keys[-1]) if keys.size else 0)
+
+
+def segmentation_mask(seg: torch.Tensor, erode: Optional[str] = None, connectivity: int = 1, background: int = 0,
+                      table=None, unassigned=0, out_dtype: Optional[torch.dtype] = None, force_search: bool = False,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pass of pxsom_segmask over a ``[H, W]`` label image in HBM (rows contiguous, any row stride): optional border
+    erosion (``erode`` "thick" / "inner": skimage's find_boundaries with ``connectivity`` and ``background``; boundary
+    pixels become 0), then the optional lookup ``table`` of :func:`segmask_table` (label cast to int32, ``unassigned``
+    where the table has no entry), stored as ``out_dtype`` (int16, int32, float64 or the image's dtype; default: the
+    image's).  ``force_search`` takes the binary-search route even where a dense LUT would fit."""
+    h, w, ld = _label_image(seg, "seg")
+    if erode not in SEG_ERODE:
+        raise NotImplementedError(f"erosion mode {erode!r}: only 'thick' and 'inner' are implemented")
+    connectivity = max(int(connectivity), 1)        # scipy's generate_binary_structure treats < 1 as 1
+    if out_dtype is None:
+        out_dtype = seg.dtype
+    if out_dtype != seg.dtype and out_dtype not in (torch.int16, torch.int32, torch.float64):
+        raise ValueError("out_dtype must be int16, int32, float64 or the image's dtype")
+    code_out = SEG_F64 if out_dtype == torch.float64 else SEG_DTYPES[out_dtype]
+    out = _rows_plane(out, h, w, out_dtype, seg.device, "out")
+    ldo = _ld(out)
+    lib = _capi.lib()
+    if table is None:
+        keys = values = None
+        n_keys, kmin, kmax = -1, 0, 0
+    else:
+        keys, values, kmin, kmax = table
+        n_keys = keys.numel()
+        if values.dtype != (torch.float64 if out_dtype == torch.float64 else torch.int32):
+            raise ValueError("table values must be float64 for a float64 output, int32 otherwise")
+    wsb = 0 if force_search or n_keys <= 0 else lib.pxsom_segmask_workspace_bytes(n_keys, kmin, kmax)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=seg.device) if wsb else None
+    _capi.call("pxsom_segmask", seg.data_ptr(), SEG_DTYPES[seg.dtype], h, w, ld, SEG_ERODE[erode], connectivity, int(background),
+               keys.data_ptr() if keys is not None else None, values.data_ptr() if values is not None else None,
+               n_keys, kmin, kmax, float(unassigned), out.data_ptr(), code_out, ldo,
+               ws.data_ptr() if ws is not None else None, wsb,
+               SEGMASK_FORCE_SEARCH if force_search else 0, _capi.stream_ptr())
+    return out
+
+
+BLUR_MAX_RADIUS = 64                     # kMaxRadius of csrc/pxsom_pre.hip
+BLUR_SIGMA_LIMIT = 16.125                # int(4 sigma + 0.5) <= 64  <=>  sigma < 16.125
+
+
+def check_blur_sigma(sigma: float) -> None:
+    """NotImplementedError for a sigma whose radius the device blur does not take (sigma >= 16.125)."""
+    if float(sigma) > 1e-15 and int(4.0 * float(sigma) + 0.5) > BLUR_MAX_RADIUS:
+        raise NotImplementedError("gaussian blur on the device: sigma %r is beyond the radius limit "
+                                  "(sigma < %g, radius <= %d)" % (sigma, BLUR_SIGMA_LIMIT, BLUR_MAX_RADIUS))
+
+
+BLUR_MODES = {"reflect": 0, "nearest": 1}          # include/pxsom.h PXSOM_BLUR_REFLECT / PXSOM_BLUR_NEAREST
+
+
+def _blur_plane(plane: torch.Tensor, sigma: float, mode: str, out, tmp, mode_entry: bool) -> torch.Tensor:
+    """The body of both plane blurs; ``mode_entry``: through pxsom_gaussian_blur_plane_mode."""
+    if mode not in BLUR_MODES:
+        raise ValueError("mode must be 'reflect' or 'nearest', got %r" % (mode,))
+    if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in PLANE_MODE_DTYPES:
+        raise ValueError("plane must be a contiguous 2-D uint8 / int16 / uint16 / int32 / float32 / float64 HBM tensor")
+    h, w = plane.shape
+    if h == 0 or w == 0:
+        raise ValueError("plane must not be empty")
+    check_blur_sigma(sigma)
+    out = _like_plane(out, plane, "out")
+    if float(sigma) <= 1e-15:
+        if out.data_ptr() != plane.data_ptr():
+            out.copy_(plane)
+        return out
+    tmp = _like_plane(tmp, plane, "tmp")
+    weights, radius = gaussian_kernel1d(float(sigma))
+    args = (plane.data_ptr(), out.data_ptr(), tmp.data_ptr(), h, w, PLANE_MODE_DTYPES[plane.dtype], weights.ctypes.data, radius)
+    if mode_entry:
+        _capi.call("pxsom_gaussian_blur_plane_mode", *args, BLUR_MODES[mode], _capi.stream_ptr())
+    else:
+        _capi.call("pxsom_gaussian_blur_plane", *args, _capi.stream_ptr())
+    return out
+
+
+def gaussian_blur_plane(plane: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None,
+                        tmp: Optional[torch.Tensor] = None, mode: str = "reflect") -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(plane, sigma, mode=mode) of a contiguous ``[H, W]`` HBM plane in its own dtype (uint8,
+    int16, uint16, int32, float32 or float64): each pass stored in that dtype, as scipy stores it.  sigma <= 1e-15 skips
+    both axes (scipy's rule): the result is a copy.  ``out`` may be ``plane`` itself.  ``mode``: scipy's border, "reflect"
+    (the default) or "nearest".  The default mode on the five dtypes up to float32 is pxsom_gaussian_blur_plane, route and
+    bits as before the keyword existed; "nearest", and float64 planes (which this function used to refuse) under either
+    mode, go to pxsom_gaussian_blur_plane_mode."""
+    return _blur_plane(plane, sigma, mode, out, tmp, mode != "reflect" or plane.dtype == torch.float64)
+
+
+def gaussian_blur_plane_mode(plane: torch.Tensor, sigma: float, mode: str, out: Optional[torch.Tensor] = None,
+                             tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(plane, sigma, mode=mode) through pxsom_gaussian_blur_plane_mode: the plane blur of
+    :func:`gaussian_blur_plane` with the border "reflect" or "nearest" and float64 planes beside the others."""
+    return _blur_plane(plane, sigma, mode, out, tmp, True)
+
+
+def zero_by_segmentation(img: torch.Tensor, seg: torch.Tensor, exclude: bool = True) -> torch.Tensor:
+    """In place: ``img[seg > 0] = 0`` (``exclude``) or ``img[seg == 0] = 0`` for a contiguous HBM image (uint8, int16,
+    uint16, int32 or float32) and a contiguous segmentation of the same shape (uint8 .. int64)."""
+    if not img.is_cuda or not img.is_contiguous() or img.dtype not in PLANE_DTYPES:
+        raise ValueError("img must be a contiguous uint8 / int16 / uint16 / int32 / float32 HBM tensor")
+    if not seg.is_cuda or not seg.is_contiguous() or seg.dtype not in SEG_DTYPES:
+        raise ValueError("seg must be a contiguous uint8 / int16 / uint16 / int32 / uint32 / int64 HBM tensor")
+    if seg.shape != img.shape:
+        raise ValueError("img and seg must have the same shape, got %s and %s" % (tuple(img.shape), tuple(seg.shape)))
+    _capi.call("pxsom_zero_by_seg", img.data_ptr(), PLANE_DTYPES[img.dtype], seg.data_ptr(), SEG_DTYPES[seg.dtype],
+               img.numel(), 1 if exclude else 0, _capi.stream_ptr())
+    return img
+
+
+# ---- object masks (K16): labelling, the area passes, the foreground predicates ----------------------------------------
+SELECT_FILL, SELECT_KEEP = 0, 1                      # include/pxsom.h PXSOM_SELECT_*
+BIN_POSITIVE, BIN_LEVEL, BIN_LOCAL = 0, 1, 2         # PXSOM_BIN_*
+CCL_TILE = 64                                        # kTile of csrc/pxsom_ccl.hip
+
+
+def label_components(fg: torch.Tensor, connectivity: int, invert: bool = False, out: Optional[torch.Tensor] = None,
+                     capacity: Optional[int] = None):
+    """``skimage.measure.label(fg != 0, connectivity=connectivity)`` of a ``[H, W]`` uint8 / bool HBM plane (rows
+    contiguous, any row stride); with ``invert`` the pixels equal to 0 are the foreground.  Returns ``(labels, n, areas)``,
+    all in HBM: ``labels`` int32 ``[H, W]`` (``out`` if given: rows contiguous, any row stride), background 0, components
+    numbered by their first pixel in raster order; ``n`` int32 ``[1]``, the count; ``areas`` int32 ``[capacity]`` with
+    ``areas[0]`` the background pixels (default capacity: every image's worst case, ``(H W + 1) // 2 + 1``)."""
+    fg = _binary_plane(fg, "fg")
+    h, w = fg.shape
+    if connectivity not in (1, 2):
+        raise ValueError("connectivity must be 1 or 2, got %r" % (connectivity,))
+    labels = _label_plane(out, h, w, fg.device, "out")
+    capacity = (h * w + 1) // 2 + 1 if capacity is None else int(capacity)
+    n = torch.empty(1, dtype=torch.int32, device=fg.device)
+    areas = torch.empty(capacity, dtype=torch.int32, device=fg.device)
+    lib = _capi.lib()
+    wsb = lib.pxsom_label_components_workspace_bytes(h, w)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=fg.device)
+    _capi.call("pxsom_label_components", fg.data_ptr(), h, w, _ld(fg), int(connectivity), int(bool(invert)), labels.data_ptr(),
+               _ld(labels), n.data_ptr(), areas.data_ptr(), capacity, ws.data_ptr(), wsb,
+               _capi.stream_ptr())
+    return labels, n, areas
+
+
+def components_select(labels: torch.Tensor, areas: torch.Tensor, mode: str, fg: Optional[torch.Tensor] = None,
+                      area_threshold: Optional[int] = None, min_area: int = 0, max_area: Optional[int] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pass over a label image and its area table (:func:`label_components`).
+    ``mode="fill"``: ``fg | (labels != 0 & areas[labels] < area_threshold)`` as uint8, ``labels`` being those of the
+    inverted ``fg`` under connectivity 1 -- ``morphology.remove_small_holes(fg, area_threshold)``.
+    ``mode="keep"``: ``labels`` where ``min_area <= areas[labels] <= max_area``, else 0 (int32; not renumbered);
+    ``out`` may be ``labels``."""
+    if mode not in ("fill", "keep"):
+        raise ValueError("mode must be 'fill' or 'keep', got %r" % (mode,))
+    if labels.dim() != 2 or labels.shape[0] == 0 or labels.shape[1] == 0:
+        raise ValueError("labels must be a non-empty [H, W] tensor")
+    h, w = labels.shape
+    labels = _label_plane(labels, h, w, labels.device, "labels")
+    if areas.dtype != torch.int32 or not areas.is_cuda or areas.dim() != 1 or not areas.is_contiguous() or not areas.numel():
+        raise ValueError("areas must be a contiguous int32 HBM vector")
+    lim = 2 ** 62
+    if mode == "fill":
+        if fg is None or area_threshold is None:
+            raise ValueError("mode 'fill' needs fg and area_threshold")
+        fg = _binary_plane(fg, "fg")
+        if fg.shape != (h, w):
+            raise ValueError("fg and labels must have one shape")
+        out = _rows_plane(out, h, w, torch.uint8, labels.device, "out")
+        args = (SELECT_FILL, fg.data_ptr(), _ld(fg), 0, max(-lim, min(lim, int(area_threshold))))
+    else:
+        out = _label_plane(out, h, w, labels.device, "out")
+        hi = lim if max_area is None else max(-lim, min(lim, int(np.floor(max_area))))
+        args = (SELECT_KEEP, None, 0, max(-lim, min(lim, int(np.ceil(min_area)))), hi)
+    _capi.call("pxsom_components_select", args[0], args[1], args[2], labels.data_ptr(), _ld(labels), areas.data_ptr(),
+               areas.numel(), h, w, args[3], args[4], out.data_ptr(), _ld(out),
+               _capi.stream_ptr())
+    return out
+
+
+def binarize_plane(plane: torch.Tensor, mode: int = BIN_POSITIVE, level: float = 0.0,
+                   local: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The uint8 foreground of a contiguous float32 / float64 ``[H, W]`` HBM plane: ``v > 0`` (BIN_POSITIVE),
+    ``!(v < level) & v > 0`` (BIN_LEVEL) or ``v > local`` (BIN_LOCAL, ``local`` a plane of the same dtype and shape)."""
+    if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in (torch.float32, torch.float64):
+        raise ValueError("plane must be a contiguous 2-D float32 / float64 HBM tensor")
+    if plane.numel() == 0:
+        raise ValueError("plane must not be empty")
+    if mode == BIN_LOCAL:
+        if local is None:
+            raise ValueError("BIN_LOCAL needs the local plane")
+        local = _like_plane(local, plane, "local")
+    h, w = plane.shape
+    out = torch.empty((h, w), dtype=torch.uint8, device=plane.device)
+    _capi.call("pxsom_binarize_plane", plane.data_ptr(), PLANE_MODE_DTYPES[plane.dtype], h, w, int(mode), float(level),
+               local.data_ptr() if mode == BIN_LOCAL else None, out.data_ptr(), w,
+               _capi.stream_ptr())
+    return out
+
+
+RIDGE_MAX_RADIUS, RIDGE_MAX_SCALES = 16, 8           # kRidgeMaxRadius / kRidgeMaxScales of csrc/pxsom_ridge.hip
+
+
+def ridge_sign(fg: torch.Tensor, sigmas=(1, 2, 3, 4), alpha=0.5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``skimage.filters.meijering(fg != 0, sigmas, alpha, black_ridges=False) > 0`` in skimage 0.19's statement
+    (include/pxsom.h "K22"; parity with skimage itself is unpinned) of a ``[H, W]`` uint8 / bool HBM plane (rows contiguous,
+    any row stride) -> uint8 ``[H, W]`` of 1 / 0 in HBM (``out`` if given: rows contiguous, any row stride, not ``fg``).
+    One launch of pxsom_ridge_sign.  ``H`` and ``W`` are at least 2, as np.gradient demands; up to 8 scales, each with
+    ``int(4 sigma + 0.5)`` between 1 and 16."""
+    fg = _binary_plane(fg, "fg")
+    h, w = fg.shape
+    if h < 2 or w < 2:
+        raise ValueError("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements "
+                         "are required.")
+    sigmas = list(sigmas)
+    if not 1 <= len(sigmas) <= RIDGE_MAX_SCALES:
+        raise ValueError("ridge_sign takes 1 to %d scales, got %d" % (RIDGE_MAX_SCALES, len(sigmas)))
+    if not all(float(s) > 0 and np.isfinite(float(s)) for s in sigmas) or not np.isfinite(float(alpha)):
+        raise ValueError("ridge_sign takes finite sigmas > 0 and a finite alpha, got %r and %r" % (sigmas, alpha))
+    kernels = [gaussian_kernel1d(float(s)) for s in sigmas]
+    for s, (_, radius) in zip(sigmas, kernels):
+        if not 1 <= radius <= RIDGE_MAX_RADIUS:
+            raise NotImplementedError("ridge_sign: sigma %r has radius %d outside [1, %d]" % (s, radius, RIDGE_MAX_RADIUS))
+    weights = np.ascontiguousarray(np.concatenate([k for k, _ in kernels]), dtype=np.float64)
+    radii = np.array([r for _, r in kernels], dtype=np.int32)
+    scales = np.array([float(s ** 2) for s in sigmas], dtype=np.float64)
+    out = _rows_plane(out, h, w, torch.uint8, fg.device, "out")
+    _capi.call("pxsom_ridge_sign", fg.data_ptr(), h, w, _ld(fg), weights.ctypes.data, radii.ctypes.data, scales.ctypes.data,
+               len(sigmas), float(alpha), out.data_ptr(), _ld(out), _capi.stream_ptr())
+    return out
+
+
+def object_mask(img: torch.Tensor, sigma, thresh, hole_size, min_area, max_area, local_block=None, ridge=None) -> torch.Tensor:
+    """The device chain of ``_create_object_mask`` on a ``[H, W]`` HBM image -> int32 ``[H, W]`` labels in HBM.
+    float32 / float64 images go as they are, any other dtype is cast to float64 (skimage's ``preserve_range`` rule).
+      blur       ``sigma`` None: none; else ``gaussian_filter(x, sigma, mode='nearest')`` in x's dtype
+      threshold  ``thresh`` None: ``blur > 0``; an int: ``p = np.percentile(blur[blur != 0], thresh)``, foreground
+                 ``!(blur < p) & blur > 0``; "auto": ``blur > gaussian_filter(blur, (local_block - 1) / 6, mode='reflect')``
+      holes      ``hole_size`` None: none; else background components (4-neighbourhood) of area < hole_size are filled
+      ridge      ``ridge`` None: none; a ``(sigmas, alpha)`` tuple: the foreground becomes :func:`ridge_sign` of it
+                 ("projection" objects)
+      labels     8-neighbourhood components, kept where ``min_area <= area <= max_area`` (not renumbered)
+    The percentile is the one value read back to the host: pxsom_quantile_f32 / pxsom_quantile_nonzero with their
+    ``!= 0`` keep rule (bits equal numpy's for both dtypes; a NaN pixel is dropped there where numpy's result turns NaN)."""
+    if img.dim() != 2 or not img.is_cuda or img.shape[0] == 0 or img.shape[1] == 0:
+        raise ValueError("img must be a non-empty 2-D HBM tensor")
+    x = img if img.dtype in (torch.float32, torch.float64) else img.to(torch.float64)
+    x = x.contiguous()
+    blur = x if sigma is None else gaussian_blur_plane(x, sigma, mode="nearest")
+    if thresh is None:
+        fg = binarize_plane(blur, BIN_POSITIVE)
+    elif isinstance(thresh, str):
+        if thresh != "auto" or local_block is None:
+            raise ValueError("thresh 'auto' needs local_block; got thresh=%r local_block=%r" % (thresh, local_block))
+        local = gaussian_blur_plane(blur, (float(local_block) - 1) / 6.0, mode="reflect")
+        fg = binarize_plane(blur, BIN_LOCAL, local=local)
+    else:
+        column = blur.reshape(-1, 1)
+        q = np.true_divide(thresh, 100)        # np.percentile's own division
+        p = (quantile_f32 if blur.dtype == torch.float32 else quantile_nonzero)(column, float(q), keep_mode=0)
+        fg = binarize_plane(blur, BIN_LEVEL, level=float(p.item()))
+    if hole_size is not None:
+        holes, _, hole_areas = label_components(fg, 1, invert=True)
+        fg = components_select(holes, hole_areas, "fill", fg=fg, area_threshold=hole_size)
+    if ridge is not None:
+        fg = ridge_sign(fg, ridge[0], ridge[1])
+    labels, _, areas = label_components(fg, 2)
+    return components_select(labels, areas, "keep", min_area=min_area, max_area=max_area, out=labels)
+
+
+# ---- merging object masks into the cell segmentation (K18) --------------------------------------------------------------
+
+
+def label_regions(seg: torch.Tensor, connectivity: int, out: Optional[torch.Tensor] = None,
+                  capacity: Optional[int] = None):
+    """``skimage.measure.label(seg, background=0, connectivity=connectivity)`` of a ``[H, W]`` integer HBM label plane
+    (uint8 .. int64, rows contiguous, any row stride): regions of equal non-zero value, touching regions of different
+    values kept apart.  Returns ``(labels, n, areas)`` with the conventions of :func:`label_components`; the default
+    capacity is every image's worst case, ``H W + 1``."""
+    h, w, ld = _label_image(seg, "seg")
+    if connectivity not in (1, 2):
+        raise ValueError("connectivity must be 1 or 2, got %r" % (connectivity,))
+    labels = _label_plane(out, h, w, seg.device, "out")
+    capacity = h * w + 1 if capacity is None else int(capacity)
+    n = torch.empty(1, dtype=torch.int32, device=seg.device)
+    areas = torch.empty(max(capacity, 0), dtype=torch.int32, device=seg.device)
+    lib = _capi.lib()
+    wsb = lib.pxsom_label_regions_workspace_bytes(h, w)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=seg.device)
+    _capi.call("pxsom_label_regions", seg.data_ptr(), SEG_DTYPES[seg.dtype], h, w, ld, int(connectivity), labels.data_ptr(),
+               _ld(labels), n.data_ptr(), areas.data_ptr(), capacity, ws.data_ptr(), wsb,
+               _capi.stream_ptr())
+    return labels, n, areas
+
+
+def pair_overlaps(a: torch.Tensor, b: torch.Tensor, n_a: Optional[int] = None, n_b: Optional[int] = None) -> torch.Tensor:
+    """The label pairs two ``[H, W]`` int32 HBM planes share: ``[P, 3]`` int32 in HBM, one row ``(a, b, pixels)`` per
+    pair with ``1 <= a <= n_a``, ``1 <= b <= n_b`` (default: every positive label) and ``pixels > 0``, sorted by
+    ``(a, b)``.  Two calls of pxsom_pair_overlaps: the first counts the runs of the image, which is read back and sizes
+    the list and the table of the second."""
+    h, w = _label_pair(a, b)
+    top = 2 ** 31 - 1
+    n_a, n_b = (top if v is None else int(v) for v in (n_a, n_b))
+    if not (0 <= n_a <= top and 0 <= n_b <= top):
+        raise ValueError("n_a and n_b must lie in 0 .. 2147483647")
+    lib = _capi.lib()
+    n = torch.empty(2, dtype=torch.int32, device=a.device)
+
+    def call(pairs, capacity, ws, wsb):
+        rc = lib.pxsom_pair_overlaps(a.data_ptr(), _ld(a), b.data_ptr(), _ld(b), h, w, n_a, n_b, pairs, capacity,
+                                     n.data_ptr(), ws, wsb, _capi.stream_ptr())
+        _capi.check(rc, "pxsom_pair_overlaps")
+
+    call(None, 0, None, 0)
+    runs = int(n[1].item())
+    if runs == 0:
+        return torch.empty((0, 3), dtype=torch.int32, device=a.device)
+    if runs > PAIR_CAPACITY_MAX:
+        raise NotImplementedError("pair_overlaps: %d runs of label pairs are beyond the limit %d" % (runs, PAIR_CAPACITY_MAX))
+    pairs = torch.empty((runs, 3), dtype=torch.int32, device=a.device)
+    wsb = lib.pxsom_pair_overlaps_workspace_bytes(runs)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=a.device)
+    call(pairs.data_ptr(), runs, ws.data_ptr(), wsb)
+    count = int(n[0].item())
+    if count < 0:
+        raise RuntimeError("pair_overlaps: the planes changed between the two passes")
+    return pairs[:count]
+
+
+def merge_apply(a: torch.Tensor, b: torch.Tensor, winner: torch.Tensor, removed: torch.Tensor,
+                merged: Optional[torch.Tensor] = None, remaining: Optional[torch.Tensor] = None):
+    """One pass over two ``[H, W]`` int32 HBM planes with two int32 tables indexed by ``b``:
+    ``merged = winner[b] != 0 ? winner[b] : a`` and ``remaining = removed[b] ? 0 : b`` (int32 planes, any row stride)."""
+    h, w = _label_pair(a, b)
+    for name, t in (("winner", winner), ("removed", removed)):
+        if t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or not t.is_contiguous() or not t.numel():
+            raise ValueError("%s must be a contiguous int32 HBM vector" % name)
+    if winner.numel() != removed.numel():
+        raise ValueError("winner and removed must have one length")
+    merged = _label_plane(merged, h, w, a.device, "merged")
+    remaining = _label_plane(remaining, h, w, a.device, "remaining")
+    _capi.call("pxsom_merge_apply", a.data_ptr(), _ld(a), b.data_ptr(), _ld(b), h, w, winner.data_ptr(),
+               removed.data_ptr(), winner.numel(), merged.data_ptr(), _ld(merged),
+               remaining.data_ptr(), _ld(remaining), _capi.stream_ptr())
+    return merged, remaining
+
+
+def _region_tables(labels: torch.Tensor, n: int):
+    """count [n] int64, sums [n, 2] int64 (row, column) and bbox [n, 4] int32 (closed) of the labels 1 .. n, on the host."""
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros((0, 2), np.int64), np.zeros((0, 4), np.int32)
+    h, w, ld = _label_image(labels, "labels")
+    dev = labels.device
+    keys = torch.arange(1, n + 1, dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int64, device=dev)
+    sums = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    shape = torch.empty((n, 6), dtype=torch.int64, device=dev)
+    lib = _capi.lib()
+    wsb = lib.pxsom_region_shape_workspace_bytes(n, 1, n, 0)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    _capi.call("pxsom_region_shape", labels.data_ptr(), SEG_DTYPES[labels.dtype], ld, h, w, keys.data_ptr(), n, 1, n,
+               shape.data_ptr(), count.data_ptr(), sums.data_ptr(), bbox.data_ptr(), ws.data_ptr(), wsb, 0,
+               _capi.stream_ptr())
+    return count.cpu().numpy(), sums.cpu().numpy(), bbox.cpu().numpy()
+
+
+def choose_merges(pairs: np.ndarray, object_bbox: np.ndarray, cell_count: np.ndarray, cell_sums: np.ndarray,
+                  overlap_thresh, expansion_factor):
+    """The choice of merge_masks_single on the host, in the reference's float64 statements.  ``pairs`` [P, 3] sorted by
+    (object, cell); ``object_bbox`` [n_o, 4] closed (row min, row max, column min, column max); ``cell_count`` [n_c] and
+    ``cell_sums`` [n_c, 2] of the cells 1 .. n_c.  Returns the int32 tables ``(winner, removed)`` of n_c + 1 entries:
+    the largest object that chose the cell (0: none) and whether any did.  A cell without overlap is never chosen, so
+    only the cells of the pair list are candidates; they come in ascending label within an object."""
+    n_c = len(cell_count)
+    winner = np.zeros(n_c + 1, dtype=np.int32)
+    removed = np.zeros(n_c + 1, dtype=np.int32)
+    if len(pairs) == 0:
+        return winner, removed
+    cells = pairs[:, 1].astype(np.int64) - 1
+    area = cell_count[cells].astype(np.int64)
+    centroid = cell_sums[cells].astype(np.float64) / area.astype(np.float64)[:, None]      # one division per axis
+    box = object_bbox[pairs[:, 0].astype(np.int64) - 1].astype(np.int64)
+    inside = ((centroid[:, 0] >= box[:, 0] - expansion_factor) & (centroid[:, 0] <= box[:, 1] + expansion_factor) &
+              (centroid[:, 1] >= box[:, 2] - expansion_factor) & (centroid[:, 1] <= box[:, 3] + expansion_factor))
+    overlap = pairs[:, 2].astype(np.int64)
+    meets = overlap / area > overlap_thresh / 100
+    best_object, best_overlap, best_cell = 0, 0, 0
+
+    def settle():
+        if best_cell:
+            winner[best_cell] = best_object       # objects ascend: the last to choose a cell keeps it
+            removed[best_cell] = 1
+
+    for obj, cell, ov, ok in zip(pairs[:, 0].tolist(), pairs[:, 1].tolist(), overlap.tolist(), (inside & meets).tolist()):
+        if obj != best_object:
+            settle()
+            best_object, best_overlap, best_cell = obj, 0, 0
+        if ok and ov > best_overlap:
+            best_overlap, best_cell = ov, cell
+    settle()
+    return winner, removed
+
+
+def merge_masks(object_mask: torch.Tensor, cell_mask: torch.Tensor, overlap_thresh, expansion_factor):
+    """The device chain of ``merge_masks_single`` on two ``[H, W]`` integer HBM masks of one shape -> ``(merged,
+    remaining)`` int32 planes in HBM.  Both masks are relabelled (:func:`label_regions`, 8-neighbourhood); every object,
+    in ascending order, takes the cell with the largest overlap among the cells whose centroid lies in the object's
+    closed bounding box grown by ``expansion_factor`` and whose ``overlap / area > overlap_thresh / 100`` (both compares
+    strict, the smaller label on a tie).  ``merged`` is the object labels with every chosen cell painted in its object's
+    label (the largest, when several chose it); ``remaining`` the relabelled cells without the chosen ones.  One small
+    read-back -- the pair list and the region tables -- serves the choice (:func:`choose_merges`)."""
+    if object_mask.shape != cell_mask.shape:
+        raise ValueError("Both masks must have the same shape")
+    objects, n_o, _ = label_regions(object_mask, 2)
+    cells, n_c, cell_areas = label_regions(cell_mask, 2)
+    n_o, n_c = int(n_o.item()), int(n_c.item())
+    pairs = pair_overlaps(objects, cells, n_o, n_c).cpu().numpy() if n_o and n_c else np.zeros((0, 3), np.int32)
+    if len(pairs):
+        _, _, object_bbox = _region_tables(objects, n_o)
+        _, cell_sums, _ = _region_tables(cells, n_c)
+        cell_count = cell_areas[1:n_c + 1].cpu().numpy()
+    else:
+        object_bbox, cell_sums, cell_count = np.zeros((n_o, 4), np.int32), np.zeros((n_c, 2), np.int64), np.ones(n_c, np.int64)
+    winner, removed = choose_merges(pairs, object_bbox, cell_count, cell_sums, overlap_thresh, expansion_factor)
+    dev = objects.device
+    return merge_apply(objects, cells, torch.from_numpy(winner).to(dev), torch.from_numpy(removed).to(dev))

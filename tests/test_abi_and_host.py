@@ -28,6 +28,90 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.pxsom_abi_version() == _capi.ABI_VERSION == 9
 
 
+def _header_constants():
+    """``PXSOM_NAME -> int`` for every ``#define PXSOM_NAME value`` and every enumerator of include/pxsom.h; a value is an
+    integer or the one form ``(-2147483647 - 1)``."""
+    text = open(os.path.join(ROOT, "include", "pxsom.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    value = r"(-?\d+|\(-2147483647 - 1\))"
+    found = re.findall(r"^#define (PXSOM_[A-Z0-9_]+)[ \t]+" + value + r"[ \t]*$", text, flags=re.M)
+    enums = re.findall(r"typedef enum \w+ \{(.*?)\}", text, flags=re.S)
+    assert len(enums) == 2
+    for body in enums:
+        found += re.findall(r"\b(PXSOM_[A-Z0-9_]+) = " + value + r"\s*(?:,|$)", body.strip())
+    out = {}
+    for name, v in found:
+        assert name not in out, name
+        out[name] = -2 ** 31 if v.startswith("(") else int(v)
+    return out
+
+
+def _csrc_constant(name, only=None):
+    """The integer a ``constexpr`` of csrc is defined as (``N`` or ``int64_t(1) << N``), by one regular expression over
+    every source file (or the file ``only``); all definitions found agree."""
+    csrc = os.path.join(ROOT, "ark_analysis_amd", "csrc")
+    values = set()
+    for f in sorted(os.listdir(csrc)) if only is None else [only]:
+        if f.endswith((".hip", ".h")):
+            for n, shift in re.findall(r"^constexpr \w+ %s = (?:int64_t\()?(\d+)\)?(?: << (\d+))?;" % name,
+                                       open(os.path.join(csrc, f)).read(), flags=re.M):
+                values.add(int(n) << int(shift or 0))
+    assert len(values) == 1, (name, values)
+    return values.pop()
+
+
+def test_python_constants_equal_the_header():
+    """Every Python constant that mirrors a ``#define`` or an enumerator of include/pxsom.h has the header's value, and
+    the limits the wrappers restate from csrc have the sources' values."""
+    from ark_analysis_amd import _capi, som_device as sd
+    h = _header_constants()
+    assert h["PXSOM_ABI_VERSION"] == _capi.ABI_VERSION and "PXSOM_H" not in h
+    want = {
+        "PXSOM_TRAIN_UNFUSED": sd.TRAIN_UNFUSED, "PXSOM_ASSIGN_SCREEN_ALL_LISTS": sd.ASSIGN_SCREEN_ALL_LISTS,
+        "PXSOM_ACC_PREPARED": sd.ACC_PREPARED, "PXSOM_ONLINE_INT_ABS": sd.ONLINE_INT_ABS,
+        "PXSOM_TABLES_SCRATCH_CLEAN": sd.TABLES_SCRATCH_CLEAN, "PXSOM_SEGMASK_FORCE_SEARCH": sd.SEGMASK_FORCE_SEARCH,
+        "PXSOM_CELLQUANT_FORCE_SEARCH": sd.CELLQUANT_FORCE_SEARCH, "PXSOM_REGION_FORCE_SEARCH": sd.REGION_FORCE_SEARCH,
+        "PXSOM_NUCSPLIT_FORCE_SEARCH": sd.NUCSPLIT_FORCE_SEARCH,
+        "PXSOM_SEG_F64": sd.SEG_F64,
+        "PXSOM_SEG_ERODE_NONE": sd.SEG_ERODE[None], "PXSOM_SEG_ERODE_THICK": sd.SEG_ERODE["thick"],
+        "PXSOM_SEG_ERODE_INNER": sd.SEG_ERODE["inner"],
+        "PXSOM_BLUR_REFLECT": sd.BLUR_MODES["reflect"], "PXSOM_BLUR_NEAREST": sd.BLUR_MODES["nearest"],
+        "PXSOM_SELECT_FILL": sd.SELECT_FILL, "PXSOM_SELECT_KEEP": sd.SELECT_KEEP,
+        "PXSOM_BIN_POSITIVE": sd.BIN_POSITIVE, "PXSOM_BIN_LEVEL": sd.BIN_LEVEL, "PXSOM_BIN_LOCAL": sd.BIN_LOCAL,
+        "PXSOM_MASK_BAD_LABEL": sd.MASK_BAD_LABEL, "PXSOM_MASK_BAD_PIXEL": sd.MASK_BAD_PIXEL,
+        "PXSOM_LUT_UNMAPPED": sd.LUT_UNMAPPED,
+        "PXSOM_COMM_ID_BYTES": sd.COMM_ID_BYTES, "PXSOM_P2P_HANDLE_BYTES": sd.P2P_HANDLE_BYTES,
+        "PXSOM_ONLINE_ROUTE_FIELDS": len(sd.ONLINE_ROUTE_FIELDS),
+        "PXSOM_ONLINE_LANES_PER_NODE": sd.ONLINE_LANES_PER_NODE, "PXSOM_ONLINE_THREAD_PER_NODE": sd.ONLINE_THREAD_PER_NODE,
+        "PXSOM_CELLQUANT_TOTAL": sd.CELLQUANT_MODES["total_intensity"],
+        "PXSOM_CELLQUANT_POSITIVE": sd.CELLQUANT_MODES["positive_pixel"],
+        "PXSOM_CELLQUANT_CENTER": sd.CELLQUANT_MODES["center_weighting"],
+        "PXSOM_F32": _capi.PXSOM_F32, "PXSOM_F64": _capi.PXSOM_F64, "PXSOM_F16": _capi.PXSOM_F16,
+        "PXSOM_METRIC_MANHATTAN": _capi.METRIC_MANHATTAN, "PXSOM_METRIC_EUCLIDEAN": _capi.METRIC_EUCLIDEAN,
+        "PXSOM_METRIC_CHEBYSHEV": _capi.METRIC_CHEBYSHEV, "PXSOM_METRIC_COSINE": _capi.METRIC_COSINE,
+        "PXSOM_MAX_CHANNELS": _capi.MAX_CHANNELS, "PXSOM_MAX_NODES": _capi.MAX_NODES,
+    }
+    for name, value in want.items():
+        assert h[name] == value, (name, h[name], value)
+    assert len(sd.SEG_ERODE) == 3 and len(sd.BLUR_MODES) == 2 and len(sd.CELLQUANT_MODES) == 3
+    assert _capi.METRICS == tuple(sorted(v for k, v in h.items() if k.startswith("PXSOM_METRIC_")))
+    # the status names: exactly the enumerators of pxsom_status
+    assert _capi._STATUS == {v: k for k, v in h.items() if k == "PXSOM_OK" or k.startswith("PXSOM_ERR_")}
+    # the dtype-code tables: PXSOM_SEG_* by torch dtype
+    seg = {torch.uint8: "U8", torch.int16: "I16", torch.uint16: "U16", torch.int32: "I32", torch.uint32: "U32",
+           torch.int64: "I64", torch.float64: "F64", torch.float32: "F32"}
+    for table, dtypes in ((sd.SEG_DTYPES, "U8 I16 U16 I32 U32 I64"), (sd.PLANE_DTYPES, "U8 I16 U16 I32 F32"),
+                          (sd.PLANE_MODE_DTYPES, "U8 I16 U16 I32 F32 F64"),
+                          (sd.CELLQUANT_IMAGE_DTYPES, "U8 I16 U16 I32 F64 F32")):
+        assert {seg[t]: code for t, code in table.items()} == {s: h["PXSOM_SEG_" + s] for s in dtypes.split()}
+    # limits restated from the sources
+    assert _csrc_constant("kMaxRadius") == sd.BLUR_MAX_RADIUS
+    assert _csrc_constant("kTile", only="pxsom_ccl.hip") == sd.CCL_TILE
+    assert _csrc_constant("kRidgeMaxRadius") == sd.RIDGE_MAX_RADIUS
+    assert _csrc_constant("kRidgeMaxScales") == sd.RIDGE_MAX_SCALES
+    assert _csrc_constant("kMaxPairCapacity") == sd.PAIR_CAPACITY_MAX
+
+
 def test_argument_validation_without_gpu():
     """Status codes + pxsom_last_error for bad arguments (rejected before any HIP call)."""
     from ark_analysis_amd import _capi

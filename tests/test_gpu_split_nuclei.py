@@ -1,6 +1,8 @@
 """pxsom_nuclear_overlaps, pxsom_split_apply and the chain som_device.split_large_nuclei on the GPU against the numpy
 statements of tests/split_nuclei_reference.py (checked against the reference's own outputs in test_split_nuclei.py):
 every table entry and every pixel compared exactly."""
+import sys
+
 import numpy as np
 import pandas as pd
 import pytest
@@ -165,7 +167,7 @@ def test_overflow_of_a_uint8_plane_writes_nothing(gpu, monkeypatch):
 
     def never(*args, **kwargs):
         raise AssertionError("the write pass was launched")
-    monkeypatch.setattr(som_device, "split_nuclei_apply", never)
+    monkeypatch.setattr(sys.modules[som_device.split_large_nuclei.__module__], "split_nuclei_apply", never)
     with pytest.raises(ValueError, match="uint8"):
         som_device.split_large_nuclei(torch.from_numpy(cell).to(gpu), torch.from_numpy(high).to(gpu), out=out)
     assert bool((buf == SENTINEL).all())
