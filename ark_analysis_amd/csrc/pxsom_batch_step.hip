@@ -232,8 +232,12 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
         return sa.stats_prev[e];
     };
     const int upd_r = sa.thr < 0.0 ? -1 : (sa.thr > 1.0e6 ? 1000000 : (int)floor(sa.thr));
+    (void)upd_r;   // (never read, and it stays: without the line 72 of this unit's kernels come out with other instructions)
     constexpr bool bmu_only = BMU;   // (the launch picks the kernel by the pending update's threshold: launch_step)
     double sdir[CPL];   // bmu_only: this thread's words of the statistics
+    // (R11: the three branches below each carry the load loop of wv_ and the block from the clearing of the table to park_centring();
+    // either one as a lambda called three times changed all 120 instantiations, their registers included, and so did R10
+    // clear_stats_slice inside the block: 17 of them.  The three copies are kept identical by hand.)
     if (bmu_only) {
         double cnt = 0.0;
         if (tid < 2 * 64) cnt = stat((size_t)kK * c + (tid < kK ? tid : 0));
@@ -264,6 +268,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
         }
         park_centring();
         if (tid < kK) {   // tl[node] = gain (or -1: no rows, the node stays), tl[K + node] = 1 / n
+            // (R2 node_gain_inv, written out: with a call here the 48 BMU-only kernels come out with other instructions)
 #pragma clang fp contract(off)
             const double den = 0.0 + cnt;
             tl[tid] = den > 0.0 ? batch_gain(den, sa.q, sa.sat) : -1.0;
@@ -302,8 +307,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             for (int e = (int)blockIdx.x * per + tid; e < z1; e += kStepThreads) sa.stats_zero[e] = 0.0;
         }
         park_centring();
-        const double thr = sa.thr;
-        const int r = thr < 0.0 ? -1 : (thr > 1.0e6 ? 1000000 : (int)floor(thr));
+        const int r = window_radius(sa.thr);
         double md[kXD > kYD ? kXD : kYD];
 #pragma unroll
         for (int d = 0; d < (kXD > kYD ? kXD : kYD); d++) md[d] = d <= r ? 1.0 : 0.0;
@@ -392,12 +396,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
                 inv = tl[kK + node];
             } else if (sa.has_update) {
                 den = nrow[c];
-                // gain = 1 - (1-alpha)^den (batch_gain); == 1 exactly for wide windows: the node is
-                // then the window mean itself (orc_batch_update)
-                if (den > 0.0) {
-                    gain = batch_gain(den, sa.q, sa.sat);
-                    inv = 1.0 / den;
-                }
+                node_gain_inv(den, sa.q, sa.sat, gain, inv);
             }
 #pragma unroll
             for (int i = 0; i < CPL; i++) {
@@ -406,6 +405,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
                     double v = wv_[i];
                     if (gain >= 0.0) {   // (idle channel slots hold whatever word 0 held: never used)
                         const double num = bmu_only ? 0.0 + sdir[i] : nrow[ch];
+                        // (R3 node_update, written out: a call turns the gain == 1 branch into a select in all 120 instantiations)
                         v = gain == 1.0 ? num * inv : v + gain * (num * inv - v);
                     }
                     if constexpr (EXCH)
@@ -417,13 +417,7 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
                     const double vc = v - (double)mud32[i];
                     nrm += vc * vc;
                     mymax = fmax(mymax, fabs(vc));
-                    // duplicate key: the bit pattern rotated by a channel-dependent amount, xor-ed up (no multiplies:
-                    // integer multiplies run at quarter rate; a key match is verified channel by channel anyway)
-                    if constexpr (!BMU) {   // (BMU-only steps do not look for duplicates: no key)
-                        const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-                        const int rot = (7 * ch + 1) & 63;
-                        kkey ^= (bits << rot) | (bits >> ((64 - rot) & 63));
-                    }
+                    if constexpr (!BMU) kkey ^= dup_key_term(v, ch);   // (BMU-only steps do not look for duplicates: no key)
                 }
             }
         }
@@ -472,27 +466,10 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             maxabs = fmax(maxabs, red[i]);
             wn2max = fmax(wn2max, red[kStepWaves + i]);
         }
-        // scale = 2^e with maxabs*scale in [128, 256) (pxsom_prep.h) -- but a codebook that has (nearly) collapsed onto the
-        // centring vector must not blow the scale up (the rows lie where they did): at most 2^6 over what the norm of the
-        // centring vector itself would choose (no reduction of the step's own for it)
-        int e = 0;
-        if (maxabs > 0.0 && maxabs <= DBL_MAX) {
-            int ex;
-            frexp(maxabs, &ex);
-            e = 8 - ex;
-            if (mu_norm > 0.f) {
-                int exn;
-                frexpf(mu_norm, &exn);
-                if (e > 8 - exn + 6) e = 8 - exn + 6;
-            }
-            if (e > 100) e = 100;
-            if (e < -100) e = -100;
-        }
-        const double scale = ldexp(1.0, e);
-        const bool badw = hdr->bad != 0 || !(wn2max * scale * scale <= 1.0e30) || !(maxabs * scale < 256.0);   // (256: filter_cut_abs)
+        const double scale = ldexp(1.0, scale_exponent(maxabs, mu_norm));   // (capped by the centring vector's norm)
+        const bool badw = codebook_unfit(hdr->bad != 0, wn2max, maxabs, scale);
         fscale = (float)scale;
-        // rounded up by a hair; NaN / Inf / huge codebook: every row takes the exact path
-        wn_max = badw ? 0.f : (float)(sqrt(wn2max) * scale * (1.0 + 1e-6));
+        wn_max = norm_bound(wn2max, scale, badw);
         force_exact = badw;
         if (has_node) {
             // A-fragment element of (node, nq): lane (nq << 4 | m) of node block b; the last block's (q, r) grid is
@@ -503,9 +480,9 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
             for (int i = 0; i < 8; i++) {
                 float W = 0.f;
                 if (i < CPL && nq * CPL + i < c) W = (float)((wv_[i < CPL ? i : 0] - (double)mud32[i < CPL ? i : 0]) * scale);
-                const _Float16 hi = (_Float16)W;
+                const _Float16 hi = split_hi(W);
                 fhi[i] = hi;
-                flo[i] = (_Float16)(W - (float)hi);
+                flo[i] = split_lo(W, hi);
             }
             const int lf = (nq << 4) | m;
             frag_l[(b * 2 + 0) * 64 + lf] = fhi;
@@ -845,9 +822,9 @@ __global__ __launch_bounds__(kStepThreads) void batch_step_kernel(const T *__res
 // Codebooks too big for the all-in-one step kernel (K = 400 x C = 40: fragments + statistics table exceed one CU's
 // LDS; C = 100: the same): the pending update and the codebook preparation run ONCE, in one single-workgroup launch
 // (instead of copy + update + 2 clears + prep), and leave what the generic BMU search reads in the assign workspace:
-// fragments, bias, header, transposed binary64 copy.  Same arithmetic as the head of batch_step_kernel: separable
-// window sums in registers, node values / norms / duplicate keys in the registers of thread <-> (node, part),
-// duplicates by a key scan shared by the node's lanes.  1024 threads.
+// fragments, bias, header, transposed binary64 copy.  The arithmetic of the head of batch_step_kernel (the rules of
+// pxsom_codebook_rules.h): separable window sums in registers, node values / norms / duplicate keys in the registers of
+// thread <-> (node, part), duplicates by a key scan shared by the node's lanes.  1024 threads.
 // ------------------------------------------------------------------------------------------------
 constexpr int kUpdThreads = 1024, kUpdWaves = 16;
 
@@ -899,15 +876,10 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
     const int bper = (nb + (int)gridDim.x - 1) / (int)gridDim.x;
     const int b0 = (int)blockIdx.x * bper, b1 = min(b0 + bper, nb);
     const int n0 = min(16 * b0, K), n1 = min(16 * b1, K);
-    if (sa.stats_zero) {
-        const int zper = (sa.zero_count + (int)gridDim.x - 1) / (int)gridDim.x;
-        const int z1 = min(((int)blockIdx.x + 1) * zper, sa.zero_count);
-        for (int e = (int)blockIdx.x * zper + tid; e < z1; e += kUpdThreads) sa.stats_zero[e] = 0.0;
-    }
+    clear_stats_slice<kUpdThreads>(sa.stats_zero, sa.zero_count);
     PXSOM_PHASE(1);
     if (sa.has_update) {
-        const double thr = sa.thr;
-        const int r = thr < 0.0 ? -1 : (thr > 1.0e6 ? 1000000 : (int)floor(thr));
+        const int r = window_radius(sa.thr);
         // window mask as a uniform select per term (|y - y'| <= r ? 1 : 0): no table of masks to keep in registers
         if (p1) {
 #pragma unroll
@@ -941,8 +913,7 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
         if (tid < K) {
             const int xp = tid / YD, yp = tid - xp * YD;
             const double den = tl[(size_t)(yp * XD + xp) * NC + c];
-            gain_l[tid] = den > 0.0 ? batch_gain(den, sa.q, sa.sat) : -1.0;
-            tl[(size_t)(yp * XD + xp) * NC + c] = den > 0.0 ? 1.0 / den : 0.0;     // the count column now holds 1/den
+            node_gain_inv(den, sa.q, sa.sat, gain_l[tid], tl[(size_t)(yp * XD + xp) * NC + c]);     // the count column now holds 1/den
         }
         PXSOM_PHASE(4);
         __syncthreads();
@@ -959,10 +930,7 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
                     const double *nrow = tl + (size_t)(yp * XD + xp) * NC;
                     const double gain = gain_l[nd];
                     double v = wold[u];
-                    if (gain >= 0.0) {
-                        const double mean = nrow[j] * nrow[c];
-                        v = gain == 1.0 ? mean : v + gain * (mean - v);
-                    }
+                    if (gain >= 0.0) v = node_update(v, gain, nrow[j] * nrow[c]);
                     wold[u] = v;
                     if (sa.w_out && blockIdx.x == 0) sa.w_out[e] = v;
                 }
@@ -999,9 +967,7 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
             nrm += vc * vc;
             raw2 += v * v;
             mymax = fmax(mymax, fabs(vc));
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-            const int rot = (7 * ch + 1) & 63;
-            kkey ^= (bits << rot) | (bits >> ((64 - rot) & 63));
+            kkey ^= dup_key_term(v, ch);
         }
     }
     for (int m = 1; m < parts; m <<= 1) {   // the lanes of a node are adjacent: butterfly
@@ -1031,26 +997,14 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
         wn2max = fmax(wn2max, red[kUpdWaves + i]);
         raw2max = fmax(raw2max, red[2 * kUpdWaves + i]);
     }
-    int e = 0;
-    if (maxabs > 0.0 && maxabs <= DBL_MAX) {
-        int ex;
-        frexp(maxabs, &ex);
-        e = 8 - ex;
-        if (mu_norm > 0.f) {   // a codebook collapsed onto the centring vector must not blow the scale up (batch_step_kernel P4)
-            int exn;
-            frexpf(mu_norm, &exn);
-            if (e > 8 - exn + 6) e = 8 - exn + 6;
-        }
-        if (e > 100) e = 100;
-        if (e < -100) e = -100;
-    }
+    const int e = scale_exponent(maxabs, mu_norm);   // (capped by the centring vector's norm)
     const double scale = ldexp(1.0, e);
     __syncthreads();
-    const bool badw = flags[0] != 0 || !(wn2max * scale * scale <= 1.0e30) || !(maxabs * scale < 256.0);   // (256: filter_cut_abs)
+    const bool badw = codebook_unfit(flags[0] != 0, wn2max, maxabs, scale);
     if (tid == 0 && blockIdx.x == 0) {
         hdr_g->amb_count = 0;
         hdr_g->scale = (float)scale;
-        hdr_g->wn_max = badw ? 0.f : (float)(sqrt(wn2max) * scale * (1.0 + 1e-6));
+        hdr_g->wn_max = norm_bound(wn2max, scale, badw);
         hdr_g->force_exact = badw ? 1 : 0;
         hdr_g->tol_rel = sa.tol_rel;
         hdr_g->tol_rel_coarse = sa.tol_rel + 2.5f * 0x1.004p-10f;   // (the register-resident filter's first stage; not used by the shapes this kernel serves)
@@ -1061,14 +1015,8 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
         hdr_g->cpl = cpl;
         hdr_g->idx_bits = idx_bits;
         hdr_g->node_bits = idx_bits;
-        // (the screened exact kernel's rounding bound is on the raw vectors)
-        hdr_g->wn_raw = badw ? 0.f : (float)(sqrt(raw2max) * (1.0 + 1e-6));
-        // a row the filter vouches for has |x_j * scale| < x_limit + max_j |mu_s_j| (pxsom_prep.h)
-        double mumax = 0.0;
-        for (int j = 0; j < (c < kFilterMaxChannels ? c : kFilterMaxChannels); j++) mumax = fmax(mumax, fabs((double)s_mu[j]) * scale);
-        int t = 0;
-        while (t < 60 && !(60000.0 + mumax <= ldexp(65536.0, t))) t++;
-        hdr_g->fix_exp = e - t;
+        hdr_g->wn_raw = norm_bound(raw2max, 1.0, badw);
+        hdr_g->fix_exp = e - fix_exp_shift(s_mu, c, scale);
         hdr_g->centred = sa.mu32 ? 1 : 0;
     }
     if (blockIdx.x == 0 && tid < kFilterMaxChannels) hdr_g->mu_s[tid] = (float)((double)s_mu[tid] * scale);
@@ -1098,8 +1046,9 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
     }
     PXSOM_PHASE(8);
     __syncthreads();
-    // ---- what the generic BMU search reads: fragments, bias, transposed copy (pxsom_prep.h layouts)
-    if (npk > 0) {   // packed K axis (pxsom_assign.h packed_k; pxsom_prep.h holds the same loop)
+    // ---- what the generic BMU search reads: fragments, bias, transposed copy.  (R12: these are prep_body's output loops over the
+    // blocks [b0, b1) -- written out in both places: as one function template each they changed both callers' kernels)
+    if (npk > 0) {   // packed K axis (pxsom_assign.h packed_k)
         const int g8 = c / 8;
         for (int f = tid; f < (b1 - b0) * npk * 64; f += kUpdThreads) {
             const int fl = f & 63, m = (f >> 6) % npk, b = b0 + (f >> 6) / npk;
@@ -1110,8 +1059,8 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
             for (int i = 0; i < 8; i++) {
                 float W = 0.f;
                 if (term < 2 && nd < K) W = (float)(tl[(size_t)nd * c + ch0 + i] * scale);   // (packed K: binary16 rows, never centred)
-                const _Float16 hi = (_Float16)W;
-                fr[i] = term == 0 ? hi : (_Float16)(W - (float)hi);
+                const _Float16 hi = split_hi(W);
+                fr[i] = term == 0 ? hi : split_lo(W, hi);
             }
             wfrag[(size_t)(b * npk + m) * 64 + fl] = fr;
         }
@@ -1127,9 +1076,9 @@ __global__ __launch_bounds__(kUpdThreads) void batch_update_prep_kernel(StepArgs
             const int ch = h * 4 * cpl + q * cpl + i;
             float W = 0.f;
             if (i < cpl && ch < c && nd < K) W = (float)((tl[(size_t)nd * c + ch] - (double)s_mu[ch < kFilterMaxChannels ? ch : 0]) * scale);
-            const _Float16 hi = (_Float16)W;
+            const _Float16 hi = split_hi(W);
             fhi[i] = hi;
-            flo[i] = (_Float16)(W - (float)hi);
+            flo[i] = split_lo(W, hi);
         }
         wfrag[(size_t)(b * nsteps + 2 * h) * 64 + fl] = fhi;
         wfrag[(size_t)(b * nsteps + 2 * h + 1) * 64 + fl] = flo;

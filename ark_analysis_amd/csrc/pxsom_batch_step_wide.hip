@@ -210,14 +210,12 @@ __global__ __launch_bounds__(kWideThreads) void batch_step_wide_kernel(const T *
         ctl->q_n = 0u;
         ctl->bad = 0;
     }
+    // (a variant of R1 window_radius -- no update or thr < 1: 0 --, written out: through the rule the kernels' registers changed)
     const int r = !sa.has_update ? 0 : (sa.thr > 1.0e6 ? 1000000 : (sa.thr >= 1.0 ? (int)floor(sa.thr) : 0));
-    if (sa.stats_zero) {
-        const int zper = (sa.zero_count + (int)gridDim.x - 1) / (int)gridDim.x;
-        const int z1 = min(((int)blockIdx.x + 1) * zper, sa.zero_count);
-        for (int e = (int)blockIdx.x * zper + tid; e < z1; e += kWideThreads) sa.stats_zero[e] = 0.0;
-    }
+    clear_stats_slice<kWideThreads>(sa.stats_zero, sa.zero_count);
     if (r == 0) {
         if (tid < ws.kp) {
+            // (R2 node_gain_inv, written out here and below: with a call at either place all 8 kernels come out with other instructions)
             const double den = (tid < k && sa.has_update) ? sa.stats_prev[(size_t)kc + tid] : 0.0;
             gain_l[tid] = den > 0.0 ? batch_gain(den, sa.q, sa.sat) : -1.0;
             inv_l[tid] = den > 0.0 ? 1.0 / den : 0.0;
@@ -241,10 +239,7 @@ __global__ __launch_bounds__(kWideThreads) void batch_step_wide_kernel(const T *
                     const int node = (ws.cmagic ? (int)__umulhi((unsigned)e, ws.cmagic) : e), j = e - node * c;
                     const double gain = gain_l[node];
                     double v = wo[u];
-                    if (gain >= 0.0) {
-                        const double mean = sv[u] * inv_l[node];
-                        v = gain == 1.0 ? mean : v + gain * (mean - v);
-                    }
+                    if (gain >= 0.0) v = node_update(v, gain, sv[u] * inv_l[node]);
                     wl[(size_t)node * cs + j] = v;
                     if (sa.w_out && blockIdx.x == 0) sa.w_out[e] = v;
                 }
@@ -288,7 +283,7 @@ __global__ __launch_bounds__(kWideThreads) void batch_step_wide_kernel(const T *
         pass(yd, xd, yd * cs, false);
         __syncthreads();
         if (tid < ws.kp) {
-            const double den = tid < k ? wl[(size_t)tid * cs + c] : 0.0;
+            const double den = tid < k ? wl[(size_t)tid * cs + c] : 0.0;   // (R2, written out: see above)
             gain_l[tid] = den > 0.0 ? batch_gain(den, sa.q, sa.sat) : -1.0;
             inv_l[tid] = den > 0.0 ? 1.0 / den : 0.0;
         }
@@ -299,10 +294,7 @@ __global__ __launch_bounds__(kWideThreads) void batch_step_wide_kernel(const T *
             if (e < kc) {
                 const int node = (ws.cmagic ? (int)__umulhi((unsigned)e, ws.cmagic) : e), j = e - node * c;
                 const double gain = gain_l[node];
-                if (gain >= 0.0) {
-                    const double mean = wl[(size_t)node * cs + j] * inv_l[node];
-                    wold[u] = gain == 1.0 ? mean : wold[u] + gain * (mean - wold[u]);
-                }
+                if (gain >= 0.0) wold[u] = node_update(wold[u], gain, wl[(size_t)node * cs + j] * inv_l[node]);
             }
         }
         __syncthreads();
@@ -356,22 +348,10 @@ __global__ __launch_bounds__(kWideThreads) void batch_step_wide_kernel(const T *
         maxabs = fmax(maxabs, red[i]);
         wn2max = fmax(wn2max, red[kWideWaves + i]);
     }
-    int sexp = 0;
-    if (maxabs > 0.0 && maxabs <= DBL_MAX) {
-        int ex;
-        frexp(maxabs, &ex);
-        sexp = 8 - ex;
-        if (mu_norm > 0.f) {   // a codebook collapsed onto the centring vector must not blow the scale up (pxsom_batch_step.hip P4)
-            int exn;
-            frexpf(mu_norm, &exn);
-            if (sexp > 8 - exn + 6) sexp = 8 - exn + 6;
-        }
-        sexp = max(-100, min(100, sexp));
-    }
-    const double scale_d = ldexp(1.0, sexp);
-    const bool badw = ctl->bad != 0 || !(wn2max * scale_d * scale_d <= 1.0e30) || !(maxabs * scale_d < 256.0);   // (256: filter_cut_abs)
+    const double scale_d = ldexp(1.0, scale_exponent(maxabs, mu_norm));   // (capped by the centring vector's norm)
+    const bool badw = codebook_unfit(ctl->bad != 0, wn2max, maxabs, scale_d);
     const float scale = (float)scale_d;
-    const float wn_max = badw ? 0.f : (float)(sqrt(wn2max) * scale_d * (1.0 + 1e-6));
+    const float wn_max = norm_bound(wn2max, scale_d, badw);
     const bool force_exact = badw;
     const float x_limit = 60000.0f;
     // A-fragments: frag[(b * 2 nch + 2 h) * 64 + lane] hi, + 1: lo; lane (q << 4 | m) <-> node 16 b + m, slot i of lane group q in
@@ -385,9 +365,9 @@ __global__ __launch_bounds__(kWideThreads) void batch_step_wide_kernel(const T *
             const int ch = h * 4 * cpl + q * cpl + i;
             float W = 0.f;
             if (i < cpl && ch < c && node < k) W = (float)((wl[(size_t)node * cs + ch] - (double)mu_s[ch]) * scale_d);
-            const _Float16 hi = (_Float16)W;
+            const _Float16 hi = split_hi(W);
             fhi[i] = hi;
-            flo[i] = (_Float16)(W - (float)hi);
+            flo[i] = split_lo(W, hi);
         }
         frag[(size_t)(b * 2 * NCH + 2 * h) * 64 + fl] = fhi;
         frag[(size_t)(b * 2 * NCH + 2 * h + 1) * 64 + fl] = flo;

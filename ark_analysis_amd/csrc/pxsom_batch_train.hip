@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pxsom_assign.h"
+#include "pxsom_codebook_rules.h"
 #include "pxsom_common.h"
 #include "pxsom_sums.h"
 #include "pxsom_wave.h"
@@ -33,13 +34,13 @@ __global__ __launch_bounds__(256) void batch_update_kernel(double *w, int xdim, 
     extern __shared__ __attribute__((aligned(16))) char upd_smem[];
     const int k = blockIdx.x, tid = threadIdx.x;
     // the OTHER statistics buffer (the next accumulate's target) is cleared here, a slice per workgroup
+    // (R10 clear_stats_slice in unsigned arithmetic, written out: through the rule this kernel comes out with other instructions)
     if (zero_count > 0) {
         const int per = (zero_count + gridDim.x - 1) / gridDim.x;
         for (int e = k * per + tid; e < min((k + 1) * per, zero_count); e += 256) zero_out[e] = 0.0;
     }
     const int kx = k / ydim, ky = k % ydim;
-    // nodes b with max(|dx|, |dy|) <= thr  <=>  |dx|, |dy| <= floor(thr)   (integer distances)
-    const int r = thr < 0.0 ? -1 : (thr > 1.0e6 ? 1000000 : (int)floor(thr));
+    const int r = pxsom_bmu::window_radius(thr);
     const int x0 = kx - r < 0 ? 0 : kx - r, x1 = kx + r > xdim - 1 ? xdim - 1 : kx + r;
     const int y0 = ky - r < 0 ? 0 : ky - r, y1 = ky + r > ydim - 1 ? ydim - 1 : ky + r;
     // The window rows x0..x1 are contiguous in node order: stage their statistics in LDS with every
@@ -86,9 +87,7 @@ __global__ __launch_bounds__(256) void batch_update_kernel(double *w, int xdim, 
         if (den > 0.0) {
             // 1 - (1-alpha)^den by binary exponentiation, 1 - alpha formed on the host (batch_gain; orc_batch_update)
             const double gain = pxsom_bmu::batch_gain(den, q, sat), inv = 1.0 / den;
-            // gain == 1 exactly (wide windows): the node is the window mean itself, so nodes sharing a window are
-            // bit-identical (and masked as duplicates by prep) instead of one ulp apart (orc_batch_update)
-            w[(size_t)k * c + j] = gain == 1.0 ? num * inv : wv + gain * (num * inv - wv);
+            w[(size_t)k * c + j] = pxsom_bmu::node_update(wv, gain, num * inv);
         } else if (w_src != w) {
             w[(size_t)k * c + j] = wv;
         }

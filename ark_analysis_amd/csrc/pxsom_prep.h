@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "pxsom_assign.h"
+#include "pxsom_codebook_rules.h"
 #include "pxsom_wave.h"
 
 namespace pxsom_bmu {
@@ -128,6 +129,7 @@ __device__ __forceinline__ void prep_body(const double *wl, int k, int c, Assign
             sum += v * v;
             raw2 += vr * vr;
             mymax = fmax(mymax, fabs(v));
+            // (not R4 dup_key_term, on purpose: keys never leave a unit, so this hash need not be the step kernels')
             const unsigned long long hb = (unsigned long long)__double_as_longlong(vr) * 0x9E3779B97F4A7C15ull +
                                           (unsigned long long)(j + 1) * 0xC2B2AE3D27D4EB4Full;
             key ^= hb ^ (hb >> 29);
@@ -169,8 +171,8 @@ __device__ __forceinline__ void prep_body(const double *wl, int k, int c, Assign
         wn2max = fmax(wn2max, s_red[NW + i]);
         raw2max = fmax(raw2max, s_red[2 * NW + i]);
     }
-    // scale = 2^e with maxabs*scale in [128, 256): fp16 keeps 11 significant bits there and the
-    // low halves of the split stay normal down to |x| ~ 1e-4 * maxabs.
+    // (R5 scale_exponent(maxabs, the cap's norm) with the cap taken from sqrt(raw2max) under `center`, written out: a call selects
+    // between the norm and "no cap" before the exponent is taken, and bmu_prep_kernel and the accumulating filter's kernels change)
     int e = 0;
     if (maxabs > 0.0 && maxabs <= DBL_MAX) {
         int ex;
@@ -190,12 +192,10 @@ __device__ __forceinline__ void prep_body(const double *wl, int k, int c, Assign
     const double scale = ldexp(1.0, e);
     PXSOM_PHASE_ANY(3);
     if (tid == 0) {
-        // (maxabs * scale < 256 is what filter_cut_abs counts on: it fails only where the exponent clamp above bit)
-        const bool badw = s_bad != 0 || !(wn2max * scale * scale <= 1.0e30) || !(maxabs * scale < 256.0);
+        const bool badw = codebook_unfit(s_bad != 0, wn2max, maxabs, scale);
         hdr->amb_count = 0;
         hdr->scale = (float)scale;
-        // rounded up by a hair; an infinite wn_max makes every row take the exact path
-        hdr->wn_max = badw ? 0.f : (float)(sqrt(wn2max) * scale * (1.0 + 1e-6));
+        hdr->wn_max = norm_bound(wn2max, scale, badw);
         hdr->force_exact = badw ? 1 : 0;  // NaN/Inf/huge codebook: every row takes the exact path
         // coefficient of the rigorous |filter - exact| bound, see DESIGN.md "K7 error bound":
         //   index packing 2^-(23-idx_bits) (idx_bits low mantissa bits replaced), the matrix unit's group additions
@@ -219,15 +219,9 @@ __device__ __forceinline__ void prep_body(const double *wl, int k, int c, Assign
         hdr->cpl = cpl;
         hdr->idx_bits = idx_bits;
         hdr->node_bits = node_bits;
-        hdr->wn_raw = badw ? 0.f : (float)(sqrt(raw2max) * (1.0 + 1e-6));
+        hdr->wn_raw = norm_bound(raw2max, 1.0, badw);
         hdr->centred = center ? 1 : 0;
-        // a row the filter vouches for has |x' * scale|_2 < x_limit, hence |x_j * scale| < x_limit + max_j |mu_s_j|:
-        // below 2^(16 + t) for the smallest such t >= 0
-        double mumax = 0.0;
-        for (int j = 0; j < (c < kFilterMaxChannels ? c : kFilterMaxChannels); j++) mumax = fmax(mumax, fabs(s_mud[j]) * scale);
-        int t = 0;
-        while (t < 60 && !(60000.0 + mumax <= ldexp(65536.0, t))) t++;
-        hdr->fix_exp = e - t;
+        hdr->fix_exp = e - fix_exp_shift(s_mud, c, scale);
     }
     for (int j = tid; j < kFilterMaxChannels; j += NT) hdr->mu_s[j] = (float)(s_mud[j] * scale);
 
@@ -246,8 +240,8 @@ __device__ __forceinline__ void prep_body(const double *wl, int k, int c, Assign
             for (int i = 0; i < 8; i++) {
                 float W = 0.f;
                 if (term < 2 && node < k) W = (float)(wl[(size_t)node * c + ch0 + i] * scale);
-                const _Float16 hi = (_Float16)W;
-                fr[i] = term == 0 ? hi : (_Float16)(W - (float)hi);
+                const _Float16 hi = split_hi(W);
+                fr[i] = term == 0 ? hi : split_lo(W, hi);
             }
             wfrag[(size_t)(b * npk + m) * 64 + lane] = fr;
         }
@@ -263,9 +257,9 @@ __device__ __forceinline__ void prep_body(const double *wl, int k, int c, Assign
             const int ch = h * 4 * cpl + q * cpl + i;
             float W = 0.f;
             if (i < cpl && ch < c && node < k) W = (float)((wl[(size_t)node * c + ch] - s_mud[ch < kFilterMaxChannels ? ch : 0]) * scale);
-            const _Float16 hi = (_Float16)W;
+            const _Float16 hi = split_hi(W);
             fhi[i] = hi;
-            flo[i] = (_Float16)(W - (float)hi);
+            flo[i] = split_lo(W, hi);
         }
         wfrag[(size_t)(b * nsteps + 2 * h) * 64 + lane] = fhi;
         wfrag[(size_t)(b * nsteps + 2 * h + 1) * 64 + lane] = flo;

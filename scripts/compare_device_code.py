@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Is the gfx950 device code of two built trees the same?
 
-    python scripts/compare_device_code.py TREE_A TREE_B
+    python scripts/compare_device_code.py TREE_A TREE_B [--unit NAME ...]
 
 Both trees must have been built (`python -m ark_analysis_amd._build`): the objects of csrc/*.hip are read from
 csrc/_obj/.  From each object the gfx950 code object is taken (llvm-objcopy, clang-offload-bundler), disassembled
 (llvm-objdump) and its kernel descriptors read (llvm-readelf).  Compared over the whole library, whatever unit a
 kernel lives in: the set of device functions (each exactly once), every function's instruction text, and per kernel
 the VGPR / SGPR counts and the LDS and scratch sizes.  Prints the differing functions and one summary line; exit
-status 1 on any difference.  For refactors of csrc/ that must not change a kernel.
+status 1 on any difference.  For refactors of csrc/ that must not change a kernel.  --unit pxsom_batch_step compares that
+unit's object alone (several may be named): the check after each step of such a refactor, one unit rebuilt at a time.
 """
 import glob
 import os
@@ -77,13 +78,12 @@ def descriptors(co):
     return kernels
 
 
-def library(tree):
-    """(symbol -> [(unit, text)], kernel -> descriptor) over every unit of the tree"""
+def library(tree, units=()):
+    """(symbol -> [(unit, text)], kernel -> descriptor) over every unit of the tree, or over `units` alone"""
     csrc = os.path.join(tree, "ark_analysis_amd", "csrc")
     funcs, descs = {}, {}
     with tempfile.TemporaryDirectory() as tmp:
-        for src in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-            unit = os.path.basename(src)[:-4]
+        for unit in units or sorted(os.path.basename(src)[:-4] for src in glob.glob(os.path.join(csrc, "*.hip"))):
             obj = os.path.join(csrc, "_obj", unit + ".o")
             if not os.path.exists(obj):
                 sys.exit(f"{obj} is missing: build {tree} first")
@@ -97,9 +97,12 @@ def library(tree):
 
 
 def main():
-    if len(sys.argv) != 3:
+    args = sys.argv[1:]
+    units = [args[i + 1] for i, a in enumerate(args[:-1]) if a == "--unit"]
+    trees = [a for i, a in enumerate(args) if a != "--unit" and (i == 0 or args[i - 1] != "--unit")]
+    if len(trees) != 2:
         sys.exit(__doc__)
-    (fa, da), (fb, db) = library(sys.argv[1]), library(sys.argv[2])
+    (fa, da), (fb, db) = library(trees[0], units), library(trees[1], units)
     bad = []
     for sym in sorted(set(fa) | set(fb)):   # a function defined by several units: by the same number of them on both sides
         na, nb = len(fa.get(sym, [])), len(fb.get(sym, []))
