@@ -100,6 +100,12 @@ SYMBOLS = {
     "pxsom_assign_metric": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _i32, _vp]),
     "pxsom_train_online_metric": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i32, _i32, _i32, _f64, _f64,
                                          _f64, _f64, _vp, _i32, _i32, _vp]),
+    "pxsom_metric_step_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "pxsom_assign_sums_metric": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _f64, _vp, _sz,
+                                        _i32, _vp]),
+    "pxsom_batch_train_sched_metric_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32, _vp, _i32, _i32]),
+    "pxsom_batch_train_sched_metric": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32,
+                                              _i32, _f64, _f64, _f64, _f64, _f64, _vp, _sz, _i32, _vp, _i32, _vp]),
     "pxsom_train_online_route": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp]),
     "pxsom_train_online_routes": (_i32, [_i64, _vp, _vp]),
     "pxsom_segmask_workspace_bytes": (_sz, [_i64, ctypes.c_int32, ctypes.c_int32]),

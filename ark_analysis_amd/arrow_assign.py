@@ -6,7 +6,7 @@ three full copies of the table on the host before a byte reaches the GPU.  ``clu
 on the Arrow table the file reader produced:
 
     column chunks --H2D--> [C, n] f64 --transpose--> [n, C] --pxsom_normalize_columns (IEEE division, the
-    reference's ``x / norm``)--> pxsom_assign --> labels;   [n, C] --transpose--> [C, n] --D2H--> Arrow
+    reference's ``x / norm``)--> pxsom_assign (pxsom_assign_sums_metric under a SOM's ``distf`` 1 / 3 / 4) --> labels;   [n, C] --transpose--> [C, n] --D2H--> Arrow
     columns;  untouched columns (fov, row_index, ...) are passed through zero-copy.
 
 The [C, n] host block the normalised channels land in is recycled (:class:`HostBlocks`): a device-to-host copy
@@ -123,15 +123,25 @@ def label_table(som, table: pa.Table, normalize: bool, blocks: Optional[HostBloc
         norm = torch.from_numpy(som.norm_data.iloc[0].to_numpy(dtype=np.float64)).to(dev)
         som_device.normalize_columns(rows, norm, out=rows)   # element-wise, in place
     codebook = torch.from_numpy(np.ascontiguousarray(som.weights.to_numpy(dtype=np.float64))).to(dev)
-    labels, _ = som_device.assign(rows, codebook)
+    distf = getattr(som, "distf", 2)    # the distance the SOM was trained under (the weights file does not record it)
     totals = None
-    if blocks is not None:      # (the rows are in HBM now: their per-cluster sums cost 20 us, not a second file read)
-        sums, counts = som_device.cluster_sums(rows, labels, codebook.shape[0])
+    if distf != 2:
+        # FlowSOM's other distances: labels and totals from ONE pass over the rows (pxsom_assign_sums_metric); the counts are
+        # exact, the sums binary64 and unquantised
+        labels, stats = som_device.assign_sums_metric(rows, codebook, distf)
+        k = codebook.shape[0]
+        sums, counts = stats[:k * c].view(k, c), stats[k * c:].to(torch.int64)
+    else:
+        labels, _ = som_device.assign(rows, codebook)
+        if blocks is not None:  # (the rows are in HBM now: their per-cluster sums cost 20 us, not a second file read)
+            sums, counts = som_device.cluster_sums(rows, labels, codebook.shape[0])
+    if blocks is not None:
         counts_host = counts.cpu().numpy()
         totals = (tuple(feats), sums.cpu().numpy(), counts_host)
         som.som_clusters_seen.update((np.flatnonzero(counts_host) + 1).tolist())
     else:
-        som.som_clusters_seen.update(torch.unique(labels).cpu().tolist())
+        # (label 0 -- a row no node compared smaller for, under distf 1 / 3 / 4 -- is no cluster: as with ``blocks``)
+        som.som_clusters_seen.update(v for v in torch.unique(labels).cpu().tolist() if v != 0 or distf == 2)
     label_array = pa.array(labels.cpu().numpy())         # int32, like the DataFrame path
 
     replaced, release = {}, None

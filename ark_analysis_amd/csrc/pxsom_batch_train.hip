@@ -11,6 +11,7 @@
 #include "pxsom_assign.h"
 #include "pxsom_codebook_rules.h"
 #include "pxsom_common.h"
+#include "pxsom_metric_step.h"
 #include "pxsom_sums.h"
 #include "pxsom_wave.h"
 #include "pxsom_xch.h"
@@ -636,6 +637,91 @@ PXSOM_EXPORT int pxsom_batch_train_sched_from(const void *x_dev, int64_t n, int 
                          train_steps_typed<T>(xp, n, c, ldx, dtype, wbuf_dev, stats_ring_dev, xdim, ydim, sc, g_begin, g_end,
                                               num_passes, a0, a1, r0, r1, sum_quantum, reinterpret_cast<char *>(workspace_dev),
                                               flags, comm, st, g_begin == 0 ? w0_dev : nullptr));
+}
+
+// ---- the same run under FlowSOM's other distances (distf 1, 3, 4; DESIGN.md "K6m") ----------------------------------------
+// Same state conventions and schedule; a step is the pending update (launch_batch_update, which also clears the next
+// statistics buffer) followed by the prep + one-pass search-and-statistics launch of pxsom_metric_step.hip on the step's window
+// of the row dealing -- the rows are read where they lie, whatever the step's width.
+PXSOM_EXPORT size_t pxsom_batch_train_sched_metric_workspace_bytes(int64_t n, int c, int k, int dtype, int phases,
+                                                                   const int32_t *edges, int steps_per_pass, int metric)
+{
+    if (n < 0 || !pxsom::dtype_ok(dtype)) return 0;
+    if (check_sched("pxsom_batch_train_sched_metric_workspace_bytes", phases, edges, steps_per_pass)) return 0;
+    const size_t step = pxsom_metric_step_workspace_bytes(c, k, metric);
+    if (!step) return 0;
+    // behind the prepared codebook: the labels of a step's rows (the steps that take two launches: pxsom_metric_step.h)
+    const Sched sc{phases, steps_per_pass, edges};
+    return pxsom::align_up(step, 256) + (size_t)std::max<int64_t>(sc.rows_max(n), 1) * sizeof(int32_t);
+}
+
+PXSOM_EXPORT int pxsom_batch_train_sched_metric(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, const double *w0_dev,
+                                                double *wbuf_dev, double *stats_ring_dev, int xdim, int ydim, int phases,
+                                                const int32_t *edges, int steps_per_pass, int g_begin, int g_end, int num_passes,
+                                                double a0, double a1, double r0, double r1, double sum_quantum, void *workspace_dev,
+                                                size_t workspace_bytes, int flags, pxsom_comm *comm, int metric, void *stream)
+{
+    (void)flags;   // (the routes the flags choose among are the Euclidean ones)
+    if (!pxsom_metric::metric_known(metric))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG,
+                           "pxsom_batch_train_sched_metric: unknown metric %d (FlowSOM distf: 1 Manhattan, 2 Euclidean, 3 Chebyshev, "
+                           "4 cosine)", metric);
+    if (metric == PXSOM_METRIC_EUCLIDEAN)
+        return pxsom::fail(PXSOM_ERR_UNSUPPORTED,
+                           "pxsom_batch_train_sched_metric: metric 2 (Euclidean) has its own entry: pxsom_batch_train_sched_from");
+    if (comm)
+        return pxsom::fail(PXSOM_ERR_UNSUPPORTED,
+                           "pxsom_batch_train_sched_metric: no exchange inside the library under this metric (run one step per "
+                           "call and all-reduce ring[g % 3] in between)");
+    int rc = pxsom::check_matrix("pxsom_batch_train_sched_metric", x_dev, n, c, ldx, dtype);
+    if (rc) return rc;
+    if (n > 0x7fffffffLL)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_batch_train_sched_metric: n=%lld outside [0, 2^31)", (long long)n);
+    int qe = 0;
+    if (!(sum_quantum >= 0.0) || (sum_quantum > 0.0 && frexp(sum_quantum, &qe) != 0.5))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_batch_train_sched_metric: sum_quantum must be 0 or a power of two");
+    if (xdim < 1 || ydim < 1 || (int64_t)xdim * ydim > PXSOM_MAX_NODES)
+        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_batch_train_sched_metric: grid %dx%d outside [1, %d] nodes", xdim, ydim,
+                           PXSOM_MAX_NODES);
+    if ((rc = check_sched("pxsom_batch_train_sched_metric", phases, edges, steps_per_pass))) return rc;
+    if (num_passes < 1 || g_begin < 0 || g_end < g_begin || (int64_t)g_end > (int64_t)num_passes * steps_per_pass)
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_batch_train_sched_metric: steps [%d, %d) of %d passes x %d", g_begin, g_end,
+                           num_passes, steps_per_pass);
+    if (!wbuf_dev || !stats_ring_dev) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_batch_train_sched_metric: null pointer");
+    const int k = xdim * ydim;
+    const size_t need = pxsom_batch_train_sched_metric_workspace_bytes(n, c, k, dtype, phases, edges, steps_per_pass, metric);
+    if (!workspace_dev || workspace_bytes < need)
+        return pxsom::fail(PXSOM_ERR_WORKSPACE, "pxsom_batch_train_sched_metric: workspace %zu < %zu bytes", workspace_bytes, need);
+    int32_t *step_labels = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace_dev) +
+                                                       pxsom::align_up(pxsom_metric_step_workspace_bytes(c, k, metric), 256));
+    if (pxsom::row_view_active())
+        return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "pxsom_batch_train_sched_metric: the metric kernels do not take row views");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const Sched sc{phases, steps_per_pass, edges};
+    const size_t nstats = (size_t)k * (c + 1), nw = (size_t)k * c;
+    const int64_t span = (int64_t)num_passes * sc.phases;
+    const double qmagic = (dtype == PXSOM_F64 && sum_quantum > 0.0) ? 6755399441055744.0 /* 1.5 * 2^52 */ * sum_quantum : 0.0;
+    double *wbuf = wbuf_dev, *ring = stats_ring_dev;
+    for (int gg = g_begin; gg < g_end; gg++) {
+        const int g = gg % sc.steps;
+        double *w_prev = wbuf + (size_t)((gg + 1) % 2) * nw, *w_cur = wbuf + (size_t)(gg % 2) * nw;
+        double *s_prev = ring + (size_t)((gg + 2) % 3) * nstats, *s_cur = ring + (size_t)(gg % 3) * nstats,
+               *s_next = ring + (size_t)((gg + 1) % 3) * nstats;
+        if (gg == 0) {   // the run's first codebook; ring[0] (this step's statistics) and ring[1] (the next step's) are adjacent
+            if (w0_dev && w0_dev != wbuf) PXSOM_HIP_TRY(hipMemcpyAsync(wbuf, w0_dev, nw * sizeof(double), hipMemcpyDeviceToDevice, st));
+            PXSOM_HIP_TRY(hipMemsetAsync(ring, 0, 2 * nstats * sizeof(double), st));
+        } else {         // W_g from W_{g-1} and the (all-reduced) statistics of step g - 1; the same launch clears ring[(g+1) % 3]
+            double thr = 0.0, alpha = 0.0;
+            batch_schedule(sc.pos(gg - 1), span, a0, a1, r0, r1, &thr, &alpha);
+            rc = launch_batch_update(w_cur, w_prev, xdim, ydim, c, s_prev, s_prev + nw, thr, alpha, s_next, (int)nstats, st);
+            if (rc) return rc;
+        }
+        if (sc.width(g) < 1 || n == 0) continue;   // an empty step
+        rc = pxsom_metric::assign_sums_step(x_dev, n, c, ldx, dtype, w_cur, k, sc.phases, sc.e0(g), sc.e0(g) + sc.width(g), nullptr,
+                                            step_labels, s_cur, qmagic, reinterpret_cast<char *>(workspace_dev), metric, st);
+        if (rc) return rc;
+    }
+    return PXSOM_OK;
 }
 
 PXSOM_EXPORT int pxsom_batch_train_steps(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, double *wbuf_dev,

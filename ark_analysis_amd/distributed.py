@@ -50,11 +50,14 @@ class HipKernels:
         finish(steps_done, total, alpha, radius, w)   last pending update; w receives the result
     """
 
-    def __init__(self, unfused: bool = False):
+    def __init__(self, unfused: bool = False, metric: int = 2):
         from . import som_device
         self._sd = som_device
         self._state = None
         self.unfused = bool(unfused)
+        # FlowSOM's distf of the BMU search: 2 Euclidean; 1 Manhattan, 3 Chebyshev, 4 cosine (one route, no in-library
+        # exchange: the trainer all-reduces ring(g) after every step)
+        self.metric = som_device._check_metric(metric)
 
     def absmax(self, x: torch.Tensor) -> float:
         return float(self._sd.absmax(x).item()) if x.shape[0] else 0.0
@@ -62,8 +65,8 @@ class HipKernels:
     def begin(self, x: torch.Tensor, w: torch.Tensor, xdim: int, ydim: int, schedule, group=None, quantum: float = 0.0) -> None:
         n, c = x.shape
         st = self._state
-        if st is None or not st.fits(n, c, xdim, ydim, schedule, x.dtype) or st.wbuf.device != x.device:
-            st = self._state = self._sd.BatchTrainState(n, c, xdim, ydim, schedule, x.device, dtype=x.dtype)
+        if st is None or not st.fits(n, c, xdim, ydim, schedule, x.dtype, self.metric) or st.wbuf.device != x.device:
+            st = self._state = self._sd.BatchTrainState(n, c, xdim, ydim, schedule, x.device, dtype=x.dtype, metric=self.metric)
             self._rings = [st.ring[i] for i in range(3)]     # views made once: ring(g) sits in the per-step loop
         # W_0 stays where the caller holds it: the first run of steps hands it to the library, whose preparing launch copies it into
         # the state (no copy launch in front of the pass)
@@ -77,7 +80,7 @@ class HipKernels:
         # waiting inside an all-reduce the rest skipped)
         self._unfused_now = self.unfused
         self.route_agreement = None
-        if _world(group) > 1:
+        if _world(group) > 1 and self.metric == 2:   # (the other metrics have one route: nothing to agree on)
             # launch-per-phase everywhere only where the ranks DISAGREE (some could take the one-launch 10 x 10 step, some
             # not -- an oddly aligned or empty shard), or where a rank asked for it.  Where no rank can take the fused step
             # (cell SOMs, other grids) nothing is forced: the library picks among the wide one-launch step and the
@@ -100,8 +103,9 @@ class HipKernels:
     def exchange(self, group=None):
         """The in-library exchange over ``group`` (an RCCL communicator owned by libpxsom, made once per process
         group): with it ``steps(..., comm=...)`` all-reduces every step's statistics itself.  None when the
-        group is not RCCL-backed (gloo) or PXSOM_NATIVE_EXCHANGE=0: the trainer then all-reduces ``ring(g)``."""
-        return native_exchange(group)
+        group is not RCCL-backed (gloo) or PXSOM_NATIVE_EXCHANGE=0, and under metric 1 / 3 / 4 (pxsom_batch_train_sched_metric
+        takes no communicator): the trainer then all-reduces ``ring(g)``."""
+        return native_exchange(group) if self.metric == 2 else None
 
     def ring(self, g: int) -> torch.Tensor:
         return self._rings[g % 3]
@@ -122,7 +126,7 @@ class BatchSOMTrainer:
 
     def __init__(self, xdim: int, ydim: int, channels: int, device, batch_steps=None,
                  alpha_range: Sequence[float] = (0.05, 0.01),
-                 radius_range: Optional[Sequence[float]] = None, group=None, kernels=None):
+                 radius_range: Optional[Sequence[float]] = None, group=None, kernels=None, metric: int = 2):
         from .flowsom import default_radius_range
         from .schedule import resolve
         self.xdim, self.ydim, self.k, self.c = int(xdim), int(ydim), int(xdim * ydim), int(channels)
@@ -134,7 +138,12 @@ class BatchSOMTrainer:
         self.radius_range = tuple(radius_range) if radius_range is not None else \
             default_radius_range(xdim, ydim)
         self.group = group
-        self.kernels = kernels if kernels is not None else HipKernels()
+        # ``metric``: FlowSOM's distf of the BMU search (parity with pyFlowSOM unpinned).  A kernel set handed over runs its own
+        # (one without a ``metric`` attribute is Euclidean): asking for another one is refused
+        self.metric = int(getattr(kernels, "metric", 2)) if kernels is not None else int(metric)
+        if kernels is not None and int(metric) != 2 and self.metric != int(metric):
+            raise ValueError("the kernel set runs metric %d, the trainer was asked for %d" % (self.metric, int(metric)))
+        self.kernels = kernels if kernels is not None else HipKernels(metric=metric)
 
     def _sum_quantum(self, x_local: torch.Tensor) -> float:
         """binary64 rows (what the drop-in classes hand over) train reproducibly: every value joins the per-BMU sums

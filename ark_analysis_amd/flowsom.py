@@ -152,9 +152,17 @@ def _batch_backend():
     return _capi.require_gpu(), HipKernels()
 
 
+def _batch_backend_metric(distf: int):
+    """``_batch_backend`` for FlowSOM's other distances (distf 1, 3, 4): the HIP kernels with that BMU search.  (A hook of its
+    own, so that ``_batch_backend`` stays the zero-argument Euclidean one the CPU test suite swaps.)"""
+    from . import _capi
+    from .distributed import HipKernels
+    return _capi.require_gpu(), HipKernels(metric=distf)
+
+
 def som_batch(data, xdim: int = 10, ydim: int = 10, rlen: int = 1,
               alpha_range: Sequence[float] = (0.05, 0.01), radius_range=None, nodes=None, seed=None,
-              batch_steps=None) -> np.ndarray:
+              batch_steps=None, distf: int = 2) -> np.ndarray:
     """Throughput-mode SOM training (the batch rule of DESIGN.md "K6b"; oracle of record ``orc_som_batch_sched``):
     ``rlen`` passes over ``data`` -- THIS RANK's rows when a process group exists (the per-step statistics are
     all-reduced, every rank returns the same codebook), all rows otherwise -- on the schedule ``batch_steps`` names:
@@ -163,10 +171,13 @@ def som_batch(data, xdim: int = 10, ydim: int = 10, rlen: int = 1,
     Same arguments as :func:`som` otherwise.  Initial nodes: ``nodes`` if given, else
     ``rows[RandomState(seed).choice(n, K, replace=False)]`` -- of rank 0's rows when it holds at least K, else of the
     first K rows of every rank pooled in rank order (a cohort with enough rows never fails because rank 0's share is
-    short).  Not the reference's algorithm: labels equal the batch oracle's, not those of an online pyFlowSOM run."""
+    short).  Not the reference's algorithm: labels equal the batch oracle's, not those of an online pyFlowSOM run.
+    ``distf``: the distance of the BMU search -- 1 Manhattan, 2 Euclidean, 3 Chebyshev, 4 cosine (:data:`RECALLED`
+    ``"distances"``; parity with pyFlowSOM unpinned); statistics and update are the batch rule's whatever the distance."""
     import torch
     from . import distributed
-    dev, kernels = _batch_backend()
+    distf = _check_distf(distf)
+    dev, kernels = _batch_backend() if distf == 2 else _batch_backend_metric(distf)
     rank, world = distributed.context()
     arr = data if isinstance(data, torch.Tensor) else np.asarray(data)
     n, c = int(arr.shape[0]), int(arr.shape[1])
@@ -190,7 +201,7 @@ def som_batch(data, xdim: int = 10, ydim: int = 10, rlen: int = 1,
     x = _as_device_matrix(arr, dev)
     w = torch.from_numpy(np.ascontiguousarray(nodes, dtype=np.float64).reshape(k, c)).to(dev)
     trainer = distributed.BatchSOMTrainer(xdim, ydim, c, dev, batch_steps=batch_steps, alpha_range=alpha_range,
-                                          radius_range=radius_range, kernels=kernels)
+                                          radius_range=radius_range, kernels=kernels, metric=distf)
     trainer.train(x, w, num_passes=rlen)
     return w.cpu().numpy()
 

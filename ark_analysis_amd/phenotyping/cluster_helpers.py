@@ -65,9 +65,12 @@ class PixieSOMCluster(ABC):
     @abstractmethod
     def __init__(self, weights_path: pathlib.Path, columns: List[str], num_passes: int = 1,
                  xdim: int = 10, ydim: int = 10, lr_start: float = 0.05, lr_end: float = 0.01,
-                 seed=42, *, train_mode: str = "online", batch_steps=None):
+                 seed=42, *, train_mode: str = "online", batch_steps=None, distf: int = 2):
         if train_mode not in ("online", "batch"):
             raise ValueError("train_mode must be 'online' (the reference's rule) or 'batch', got %r" % (train_mode,))
+        # FlowSOM's distance code of the BMU search, in training AND labelling (1 Manhattan, 2 Euclidean, 3 Chebyshev, 4 cosine;
+        # parity with pyFlowSOM unpinned).  The weights file does not record it: this object carries it from one to the other.
+        self.distf = flowsom._check_distf(distf)
         from ..schedule import resolve
         resolve(batch_steps)     # ValueError("batch_steps ...") for anything but a positive int / "two-phase" / a schedule
         self.train_mode, self.batch_steps = train_mode, batch_steps
@@ -113,10 +116,10 @@ class PixieSOMCluster(ABC):
         args = dict(xdim=self.xdim, ydim=self.ydim, rlen=self.num_passes,
                     alpha_range=(self.lr_start, self.lr_end), seed=self.seed)
         if self.train_mode == "batch":
-            codebook = flowsom.som_batch(data=_as_f64_matrix(data), batch_steps=self.batch_steps, **args)
+            codebook = flowsom.som_batch(data=_as_f64_matrix(data), batch_steps=self.batch_steps, distf=self.distf, **args)
         else:
             # rank 0 trains, the others receive the codebook -- or rank 0's exception (never a wait without end)
-            codebook = distributed.on_rank0(lambda: flowsom.som(data=_as_f64_matrix(data), **args))
+            codebook = distributed.on_rank0(lambda: flowsom.som(data=_as_f64_matrix(data), distf=self.distf, **args))
         nodes = self.xdim * self.ydim
         self.weights = pd.DataFrame(np.asarray(codebook).reshape(nodes, -1), columns=data.columns.values)
         if rank == 0:
@@ -136,7 +139,7 @@ class PixieSOMCluster(ABC):
 
         codebook = _as_f64_matrix(self.weights)
         features = external_data[list(trained_on)]  # also puts the columns in codebook order
-        found = [flowsom.map_data_to_nodes(codebook, _as_f64_matrix(features.iloc[lo:hi]))[0]
+        found = [flowsom.map_data_to_nodes(codebook, _as_f64_matrix(features.iloc[lo:hi]), distf=self.distf)[0]
                  for lo, hi in _row_blocks(len(external_data), num_parallel_obs)]
         # an image without retained pixels gives an empty (float) vector, like the reference
         return np.concatenate(found) if found else np.empty(0)
@@ -152,9 +155,9 @@ class PixelSOMCluster(PixieSOMCluster):
                  weights_path: pathlib.Path, fovs: List[str], columns: List[str],
                  num_passes: int = 1, xdim: int = 10, ydim: int = 10,
                  lr_start: float = 0.05, lr_end: float = 0.01, seed=42, *,
-                 train_mode: str = "online", batch_steps=None):
+                 train_mode: str = "online", batch_steps=None, distf: int = 2):
         super().__init__(weights_path, columns, num_passes, xdim, ydim, lr_start, lr_end, seed,
-                         train_mode=train_mode, batch_steps=batch_steps)
+                         train_mode=train_mode, batch_steps=batch_steps, distf=distf)
         validate_paths([norm_vals_path, pixel_subset_folder])
 
         self.fovs = fovs
@@ -207,9 +210,9 @@ class CellSOMCluster(PixieSOMCluster):
     def __init__(self, cell_data: pd.DataFrame, weights_path: pathlib.Path,
                  fovs: List[str], columns: List[str], num_passes: int = 1,
                  xdim: int = 10, ydim: int = 10, lr_start: float = 0.05, lr_end: float = 0.01,
-                 seed=42, normalize=True, *, train_mode: str = "online", batch_steps=None):
+                 seed=42, normalize=True, *, train_mode: str = "online", batch_steps=None, distf: int = 2):
         super().__init__(weights_path, columns, num_passes, xdim, ydim, lr_start, lr_end, seed,
-                         train_mode=train_mode, batch_steps=batch_steps)
+                         train_mode=train_mode, batch_steps=batch_steps, distf=distf)
         self.fovs = fovs
         in_cohort = cell_data["fov"].isin(fovs)
         self.cell_data = cell_data[in_cohort].reset_index(drop=True)

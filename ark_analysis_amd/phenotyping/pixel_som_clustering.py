@@ -29,14 +29,16 @@ def train_pixel_som(fovs, channels, base_dir,
                     norm_vals_name='post_rowsum_chan_norm.feather',
                     som_weights_name='pixel_som_weights.feather', xdim=10, ydim=10,
                     lr_start=0.05, lr_end=0.01, num_passes=1, seed=42,
-                    overwrite=False, *, train_mode="online", batch_steps=None):
+                    overwrite=False, *, train_mode="online", batch_steps=None, distf=2):
     """Train the pixel SOM on the sub-sampled tables of ``base_dir/subset_dir`` and store the codebook
     in ``base_dir/som_weights_name``; returns the :class:`~.cluster_helpers.PixelSOMCluster`.
 
     Beyond the reference (keyword-only): ``train_mode="batch"`` selects the data-parallel batch rule (throughput mode;
     under ``torchrun`` the training tables are sharded by rank and the per-step statistics all-reduced) on the schedule
     ``batch_steps`` names: an int = that many equal mini-batch steps per pass, ``None`` / "two-phase" = the default
-    schedule (``ark_analysis_amd.schedule``).  The default mode is the reference's online rule."""
+    schedule (``ark_analysis_amd.schedule``).  The default mode is the reference's online rule.  ``distf``: FlowSOM's distance
+    code of the BMU search (1 Manhattan, 2 Euclidean, 3 Chebyshev, 4 cosine; parity with pyFlowSOM unpinned), kept on the returned
+    object -- the weights file does not record it -- and used again when it labels."""
     distributed.init_from_env()
     subset_root = os.path.join(base_dir, subset_dir)
     norm_file = os.path.join(base_dir, norm_vals_name)
@@ -50,7 +52,7 @@ def train_pixel_som(fovs, channels, base_dir,
     som = cluster_helpers.PixelSOMCluster(
         subset_root, norm_file, os.path.join(base_dir, som_weights_name), fovs, channels,
         num_passes=num_passes, xdim=xdim, ydim=ydim, lr_start=lr_start, lr_end=lr_end, seed=seed,
-        train_mode=train_mode, batch_steps=batch_steps)
+        train_mode=train_mode, batch_steps=batch_steps, distf=distf)
     _say("Training SOM")
     som.train_som(overwrite=overwrite)
     return som

@@ -11,7 +11,8 @@ from ._args import (PAIR_CAPACITY_MAX, PLANE_DTYPES, PLANE_MODE_DTYPES, SEG_DTYP
                     _rows_plane)
 from .som import (ACC_PREPARED, ASSIGN_SCREEN_ALL_LISTS, ONLINE_INT_ABS, ONLINE_LANES_PER_NODE, ONLINE_ROUTE_FIELDS,
                   ONLINE_THREAD_PER_NODE, TABLES_SCRATCH_CLEAN, TRAIN_UNFUSED, AssignSumsWorkspace, AssignWorkspace,
-                  BatchTrainState, absmax, assign, assign_means, assign_sums, batch_accumulate, batch_train_finish,
+                  BatchTrainState, MetricStepWorkspace, absmax, assign, assign_means, assign_sums, assign_sums_metric,
+                  batch_accumulate, batch_train_finish,
                   batch_train_fused_route, batch_train_steps, batch_update, batch_update_prepare, cluster_sums,
                   exact_sum_quantum, last_exact_rows, pair_histogram, relabel, train_online, train_online_route,
                   train_online_routes, _with_scratch_flag)

@@ -93,17 +93,20 @@ class BatchTrainState:
     """Caller-owned state of ``pxsom_batch_train_sched``: the codebook twin buffer ``wbuf`` [2, K, C], the
     rotating statistics ``ring`` [3, K*(C+1)] (float64; ``ring[g % 3]`` is what a multi-rank job all-reduces
     after step g) and the scratch workspace for ``n`` training rows of ``dtype`` (default: the widest, so that the
-    state fits any matrix) on ``schedule`` (an int: that many equal steps per pass)."""
+    state fits any matrix) on ``schedule`` (an int: that many equal steps per pass).  ``metric``: FlowSOM's distf of the run's
+    BMU search (2 Euclidean: pxsom_batch_train_sched; 1, 3, 4: pxsom_batch_train_sched_metric, whose workspace is another)."""
 
-    def __init__(self, n: int, c: int, xdim: int, ydim: int, schedule, device, dtype=torch.float64):
+    def __init__(self, n: int, c: int, xdim: int, ydim: int, schedule, device, dtype=torch.float64, metric: int = 2):
         from ..schedule import resolve
         self.n, self.c, self.xdim, self.ydim = int(n), int(c), int(xdim), int(ydim)
         self.k, self.schedule, self.dtype = self.xdim * self.ydim, resolve(schedule), dtype
+        self.metric = _check_metric(metric)
         self.batch_steps = self.schedule.steps
         self.edges = self.schedule.edges_array()            # host array handed to every call (kept alive here)
-        self.ws_bytes = _capi.lib().pxsom_batch_train_sched_workspace_bytes(
-            self.n, self.c, self.k, _capi.dtype_code(torch.empty(0, dtype=dtype)), self.schedule.phases,
-            self.edges.ctypes.data, self.schedule.steps)
+        sized = (self.n, self.c, self.k, _capi.dtype_code(torch.empty(0, dtype=dtype)), self.schedule.phases,
+                 self.edges.ctypes.data, self.schedule.steps)
+        self.ws_bytes = _capi.lib().pxsom_batch_train_sched_workspace_bytes(*sized) if self.metric == 2 else \
+            _capi.lib().pxsom_batch_train_sched_metric_workspace_bytes(*sized, self.metric)
         if self.ws_bytes == 0:
             raise _capi.PxsomError(f"unsupported batch-training shape n={n} c={c} k={self.k}")
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
@@ -111,9 +114,10 @@ class BatchTrainState:
         self.ring = torch.zeros((3, self.k * (self.c + 1)), dtype=torch.float64, device=device)
         self.quantum = 0.0      # > 0: binary64 rows join the statistics rounded to its multiples (exact, order-free sums)
 
-    def fits(self, n: int, c: int, xdim: int, ydim: int, schedule, dtype=None) -> bool:
+    def fits(self, n: int, c: int, xdim: int, ydim: int, schedule, dtype=None, metric: int = 2) -> bool:
         from ..schedule import resolve
         return (c == self.c and xdim == self.xdim and ydim == self.ydim and resolve(schedule) == self.schedule
+                and metric == self.metric
                 and n <= self.n and (dtype is None or torch.empty(0, dtype=dtype).element_size()
                                      <= torch.empty(0, dtype=self.dtype).element_size()))
 
@@ -173,17 +177,30 @@ def batch_train_steps(x: torch.Tensor, state: BatchTrainState, g_begin: int, g_e
     back to back by the library (``state.wbuf[0]`` holds W_0 before step 0; see include/pxsom.h).  ``comm``: the
     statistics of every step are sum-all-reduced over its ranks right behind the step's launch (every rank makes the
     same call).  ``w0`` (with ``g_begin == 0``): the run's first codebook where the caller holds it -- the launch that prepares the
-    run copies it into ``state.wbuf[0]`` (pxsom_batch_train_sched_from: no copy launch in front of the pass)."""
+    run copies it into ``state.wbuf[0]`` (pxsom_batch_train_sched_from: no copy launch in front of the pass).
+    ``state.metric`` 1 / 3 / 4: pxsom_batch_train_sched_metric, which has no exchange inside the library -- a ``comm`` is refused
+    (a multi-rank run makes one call per step and all-reduces ``state.ring[g % 3]`` in between)."""
+    if state.metric != 2 and comm is not None:
+        raise ValueError("no in-library exchange under metric %d: run one step per call and all-reduce the ring" % state.metric)
     n, c, ldx, dt = _matrix_args(x)
     if w0 is not None:
         w0 = _codebook(w0)
         if tuple(w0.shape) != (state.xdim * state.ydim, c):
             raise ValueError("w0 does not match the state's codebook")
-    if not state.fits(n, c, state.xdim, state.ydim, state.schedule, x.dtype):
+    if not state.fits(n, c, state.xdim, state.ydim, state.schedule, x.dtype, state.metric):
         raise ValueError("batch-training state does not fit this matrix")
     sch = state.schedule
     if int(total_steps) % sch.steps:
         raise ValueError("total_steps must be a whole number of passes")
+    if state.metric != 2:
+        _capi.call(
+            "pxsom_batch_train_sched_metric",
+            x.data_ptr(), n, c, ldx, dt, w0.data_ptr() if (w0 is not None and int(g_begin) == 0) else None,
+            state.wbuf.data_ptr(), state.ring.data_ptr(), state.xdim, state.ydim,
+            sch.phases, state.edges.ctypes.data, sch.steps, int(g_begin), int(g_end), int(total_steps) // sch.steps,
+            float(alpha_range[0]), float(alpha_range[1]), float(radius_range[0]), float(radius_range[1]), float(state.quantum),
+            state.ws.data_ptr(), state.ws_bytes, 0, None, state.metric, _capi.stream_ptr())
+        return
     _capi.call(
         "pxsom_batch_train_sched_from",
         x.data_ptr(), n, c, ldx, dt, w0.data_ptr() if (w0 is not None and int(g_begin) == 0) else None,
@@ -345,6 +362,50 @@ def assign_sums(x: torch.Tensor, w: torch.Tensor, labels: Optional[torch.Tensor]
         x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, labels.data_ptr(), sums.data_ptr(), counts.data_ptr(),
         workspace.buf.data_ptr(), workspace.bytes, flags, _capi.stream_ptr()))
     return labels, sums, counts
+
+
+class MetricStepWorkspace:
+    """Scratch for pxsom_assign_sums_metric (metric 1, 3, 4): the prepared codebook of a (c, k); any row count."""
+
+    def __init__(self, c: int, k: int, device, metric: int):
+        self.bytes = _capi.lib().pxsom_metric_step_workspace_bytes(int(c), int(k), int(metric))
+        if self.bytes == 0:
+            raise _capi.PxsomError(f"unsupported shape c={c} k={k} metric={metric} (metric 2: assign_sums / batch_accumulate)")
+        self.c, self.k, self.metric = int(c), int(k), int(metric)
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device)
+
+    def fits(self, c: int, k: int, metric: int) -> bool:
+        return c == self.c and k == self.k and metric == self.metric
+
+
+def assign_sums_metric(x: torch.Tensor, w: torch.Tensor, metric: int, labels: Optional[torch.Tensor] = None,
+                       stats: Optional[torch.Tensor] = None, quantum: float = 0.0, window=(1, 0, 1),
+                       workspace: Optional[MetricStepWorkspace] = None):
+    """BMU labels under FlowSOM's distf 1 / 3 / 4 AND the batch statistics of the labelled rows in one pass over ``x``
+    (pxsom_assign_sums_metric).  ``window`` = (phases, e0, e1): row i takes part iff e0 <= i % phases < e1; the labels of the
+    other rows are left as they are (a new ``labels`` vector starts at zero).  ``stats`` [K*C sums | K counts] float64 is ADDED
+    into (zeros if not given); ``quantum``: binary64 rows join the sums rounded to its multiples (``exact_sum_quantum``).
+    Returns ``(labels, stats)``."""
+    metric = _check_metric(metric)
+    n, c, ldx, dt = _matrix_args(x)
+    w = _codebook(w)
+    k = w.shape[0]
+    if w.shape[1] != c:
+        raise ValueError(f"codebook has {w.shape[1]} channels, matrix has {c}")
+    phases, e0, e1 = (int(v) for v in window)
+    if labels is None:
+        labels = torch.zeros(n, dtype=torch.int32, device=x.device)
+    elif labels.dtype != torch.int32 or labels.numel() != n or not labels.is_contiguous() or not labels.is_cuda:
+        raise ValueError("labels must be a contiguous int32 HBM vector with one entry per row")
+    if stats is None:
+        stats = torch.zeros(k * (c + 1), dtype=torch.float64, device=x.device)
+    elif stats.dtype != torch.float64 or stats.numel() != k * (c + 1) or not stats.is_contiguous() or not stats.is_cuda:
+        raise ValueError("stats must be a contiguous float64 HBM vector of K*(C+1) entries")
+    if workspace is None or not workspace.fits(c, k, metric):
+        workspace = MetricStepWorkspace(c, k, x.device, metric)
+    _capi.call("pxsom_assign_sums_metric", x.data_ptr(), n, c, ldx, dt, w.data_ptr(), k, phases, e0, e1, labels.data_ptr(),
+               stats.data_ptr(), float(quantum), workspace.buf.data_ptr(), workspace.bytes, metric, _capi.stream_ptr())
+    return labels, stats
 
 
 def assign_means(x: torch.Tensor, w: torch.Tensor, labels: torch.Tensor, sums: torch.Tensor, counts: torch.Tensor,

@@ -466,6 +466,53 @@ int pxsom_train_online_metric(const void *x_dev, int64_t n, int c, int64_t ldx, 
                               int xdim, int ydim, int rlen, double a0, double a1, double r0, double r1,
                               const int64_t *order_dev, int metric, int flags, void *stream);
 
+/* ---- batch training and one-pass labelling under distf 1, 3, 4 (K6m; symbols added under ABI 9, none changed) ----------
+ * pxsom_assign_sums_metric: labels AND batch statistics of a set of rows in one pass over x_dev, metric 1, 3 or 4.
+ *   rows       row i takes part iff e0 <= i % phases < e1 (the row dealing of pxsom_batch_train_sched; 1, 0, 1: every row)
+ *   labels_dev [n] int32 or NULL: pxsom_assign_metric's label of every row that takes part, bit for bit (same helpers, same
+ *              order, first strict minimum below DBL_MAX, 0 when nothing compared smaller); the other entries are left untouched
+ *   stats_dev  [k*c sums | k counts] binary64, ADDED into: a row with label b >= 1 adds its values -- binary64 rows rounded to
+ *              sum_quantum as under "Reproducible statistics" above, binary32 / binary16 rows as they are -- to sums[b-1][:]
+ *              and 1 to counts[b-1]; label-0 rows add nothing; a non-finite value of a labelled row (Chebyshev skips NaN
+ *              channels in the search) is added in binary64 like any other.  With a quantum from pxsom_exact_sum_quantum every
+ *              addition is exact: the same bits for any grid, any order, every run.  With quantum 0 the additions are binary64
+ *              in unspecified order.  Counts are always exact.
+ * One launch behind the codebook preparation of pxsom_assign_metric (the same workspace layout;
+ * pxsom_metric_step_workspace_bytes(c, k, metric), 0 for an unknown metric, metric 2 or a shape outside the limits): a grid
+ * sized to the CUs loops over the rows, each workgroup sums into a table [k*c | k] in LDS and adds its non-zero entries to
+ * stats_dev at the end.  LIMIT: a table that does not fit 160 KiB of LDS beside the staging of rows wider than 32 channels
+ * (k * (c + 1) * 8 bytes; 400 x 40 fits, 1024 x 64 does not) is not built -- every row is then added to stats_dev directly,
+ * as pxsom_cluster_sums does for such tables; same results, but SLOWER than pxsom_assign_metric + pxsom_cluster_sums (1.12 -
+ * 1.20 x at 65 536 x 64, K = 1024).  TWO LAUNCHES inside the entry -- pxsom_assign_metric, then the sums kernels with the
+ * quantum -- replace the one pass where it measured slower than that pair (cosine on rows wider than 32 channels; every metric past the
+ * LIMIT) whenever the
+ * pair can run: the window is every row and labels_dev is given (its labels are then the pair's), or, in
+ * pxsom_batch_train_sched_metric, the step is one phase or every row (its labels go to the workspace).  Same results.
+ * Checks in the order and words of pxsom_assign_metric: unknown metric PXSOM_ERR_INVALID_ARG before any HIP call; metric 2
+ * PXSOM_ERR_UNSUPPORTED (pxsom_assign_sums / pxsom_batch_accumulate are the Euclidean entries); then n, c, k, ldx, dtype, null
+ * pointers, the window (0 <= e0 < e1 <= phases), sum_quantum (0 or a power of two), the workspace, an active row view.  n == 0
+ * or no row in the window: PXSOM_OK, nothing touched.  Statement of record: tests/metric_reference.py (labels) with
+ * orc_cluster_sums / oracle_binding.quantize (statistics); parity with pyFlowSOM unpinned.
+ * pxsom_batch_train_sched_metric: pxsom_batch_train_sched_from under metric 1, 3 or 4.  State conventions unchanged
+ * (wbuf[g % 2] holds W_g; step g leaves its statistics in ring[g % 3] and clears ring[(g+1) % 3]; the g_begin == 0 call
+ * clears ring[0] and takes w0_dev); per step the pending update of step g - 1 (the launch of pxsom_batch_update), then
+ * preparation + pxsom_assign_sums_metric's launch on the step's window [edges[g], edges[g+1]) -- rows are read where they lie.
+ * Schedule position, threshold and alpha as pxsom_batch_train_sched; flags are ignored (they choose among Euclidean routes).
+ * Workspace: pxsom_batch_train_sched_metric_workspace_bytes (the prepared codebook and the labels of the largest step).
+ * comm must be NULL (PXSOM_ERR_UNSUPPORTED otherwise): a multi-rank run makes one call per step and all-reduces ring[g % 3]
+ * in between.  n < 2^31.  pxsom_batch_train_sched_finish serves every metric. */
+size_t pxsom_metric_step_workspace_bytes(int c, int k, int metric);
+int pxsom_assign_sums_metric(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, const double *w_dev, int k,
+                             int phases, int e0, int e1, int32_t *labels_dev, double *stats_dev, double sum_quantum,
+                             void *workspace_dev, size_t workspace_bytes, int metric, void *stream);
+size_t pxsom_batch_train_sched_metric_workspace_bytes(int64_t n, int c, int k, int dtype, int phases,
+                                                      const int32_t *edges_host, int steps_per_pass, int metric);
+int pxsom_batch_train_sched_metric(const void *x_dev, int64_t n, int c, int64_t ldx, int dtype, const double *w0_dev,
+                                   double *wbuf_dev, double *stats_ring_dev, int xdim, int ydim, int phases,
+                                   const int32_t *edges_host, int steps_per_pass, int g_begin, int g_end, int num_passes,
+                                   double a0, double a1, double r0, double r1, double sum_quantum, void *workspace_dev,
+                                   size_t workspace_bytes, int flags, pxsom_comm *comm, int metric, void *stream);
+
 /* ---- the launch an online training call would make (host arithmetic, no GPU call; works without a device) --------
  * pxsom_train_online[_ex] (metric 2) and pxsom_train_online_metric (1, 3, 4) pick one of their kernel forms from
  * k = xdim * ydim and c alone; this query runs the same planning function the launch runs and fills out[0 .. 6]:
