@@ -150,6 +150,10 @@ SYMBOLS = {
                                                 _i32]),
     "pxsom_split_apply": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _i64, ctypes.c_int32, ctypes.c_int32,
                                  _vp, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _i32, _vp]),
+    "pxsom_region_euler_workspace_bytes": (_sz, [_i64, ctypes.c_int32, ctypes.c_int32, _i32]),
+    "pxsom_region_euler": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _sz,
+                                  _i32, _vp]),
+    "pxsom_nearest_indices": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
 }
 
 _lib = None

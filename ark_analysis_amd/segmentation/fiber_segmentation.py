@@ -1,0 +1,334 @@
+"""The reference's ``ark.segmentation.fiber_segmentation`` from the segmented mask onward: labelling, the
+size filter, the fibre object table, the k-nearest-fibre alignment score and the FOV / tile summaries.
+
+Built here: :func:`fiber_objects` (the tail of ``segment_fibers``: ``ndi.label``, ``remove_small_objects``,
+``regionprops_table``), :func:`fiber_object_props`, :func:`fiber_object_table_from_labels` (the cohort call over saved
+``<fov>_fiber_labels.tiff`` files, ending as ``run_fiber_segmentation`` ends), :func:`calculate_fiber_alignment`,
+:func:`calculate_density`, :func:`generate_tile_stats` and :func:`generate_summary_stats`, with the reference's names,
+signatures, defaults, columns, files and errors.
+
+On the device: the labels (pxsom_label_components, pxsom_components_select), the raw integers of every object
+(pxsom_region_shape, which streams the plane and has no object-size limit, and pxsom_region_euler) and the neighbours of
+the alignment score (pxsom_nearest_indices, one launch for the whole table; the FOV's distance matrix is never built).
+The float columns come from ``regionprops_extraction.morphology`` on the host; skimage is taken by its documented
+algorithms (``orientation`` as skimage 0.19 states it) and parity with skimage itself is not pinned.  The summaries
+are pandas on the host, as in the reference.
+
+Not built: the front half of ``segment_fibers`` -- ``equalize_adapthist``, ``frangi``, ``threshold_multiotsu``, ``sobel``
+and ``watershed``.  :func:`segment_fibers`, :func:`run_fiber_segmentation` and :func:`plot_fiber_segmentation_steps` keep
+the reference's signatures, validate their paths and the channel as the reference does, and then raise
+NotImplementedError."""
+import os
+from typing import Dict, Optional
+
+import numpy as np
+import pandas as pd
+
+from .. import image_io
+from ..host_utils import list_files, list_folders, natsorted, remove_file_extensions, validate_paths, verify_in_list
+from . import regionprops_extraction as rpe
+from .marker_quantification import _as_label_plane
+
+FOV_ID = "fov"                                                                          # ark.settings
+FIBER_OBJECT_PROPS = ("label", "centroid", "major_axis_length", "minor_axis_length", "orientation", "area",
+                      "eccentricity", "euler_number")
+BUILT_OBJECT_PROPS = FIBER_OBJECT_PROPS      # what fiber_object_props builds: today exactly the default list
+NEAREST_MAX_K = 32          # som_device.nearest_indices keeps the k nearest in registers
+_LABELS_SUFFIX = "_fiber_labels.tiff"
+_TILE_PROPERTIES = ["major_axis_length", "minor_axis_length", "orientation", "area", "eccentricity", "euler_number"]
+_UNBUILT = ("the front half of fibre segmentation (equalize_adapthist, frangi, threshold_multiotsu, sobel, watershed) "
+            "is not implemented; from a segmented mask use fiber_objects, from saved <fov>_fiber_labels.tiff files "
+            "fiber_object_table_from_labels")
+
+
+# ---- device entry points (the CPU tests swap them for the numpy statements of the same contracts) -------------------
+def _nearest_indices_device(xy: np.ndarray, seg: np.ndarray, k: int) -> np.ndarray:
+    """som_device.nearest_indices on host arrays: ``xy`` [n, 2] float64, ``seg`` [F + 1] offsets -> [n, k] int32 on the
+    host."""
+    from .. import som_device
+    from ..analysis._cells import _to_device
+    return som_device.nearest_indices(_to_device(xy, np.float64), _to_device(seg, np.int64), k).cpu().numpy()
+
+
+def _region_raw_device(labels: np.ndarray) -> dict:
+    """som_device.region_moments and som_device.region_euler over a host label plane: host arrays ``keys``, ``count``,
+    ``sums``, ``bbox``, ``shape`` and ``euler``."""
+    import torch
+    from .. import _capi, som_device
+    a = np.ascontiguousarray(labels)
+    seg = torch.from_numpy(a if a.flags.writeable else a.copy()).to(_capi.require_gpu())
+    got = som_device.region_moments(seg)
+    got["euler"] = som_device.region_euler(seg, keys=got["keys"])
+    return {name: v.cpu().numpy() for name, v in got.items()}
+
+
+def _label_and_filter_device(mask: np.ndarray, min_size: int) -> np.ndarray:
+    """``ndi.label(mask)`` (4-connected) with the components under ``min_size`` pixels removed, not renumbered: int32."""
+    import torch
+    from .. import _capi, som_device
+    fg = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).view(np.uint8)).to(_capi.require_gpu())
+    labels, _, areas = som_device.label_components(fg, connectivity=1)
+    return som_device.components_select(labels, areas, "keep", min_area=min_size, out=labels).cpu().numpy()
+
+
+# ---- the object table -------------------------------------------------------------------------------------------------
+def _object_columns(object_properties):
+    names = []
+    for p in object_properties:
+        if p not in BUILT_OBJECT_PROPS:
+            raise NotImplementedError("object_properties: %r is not implemented; the built properties are %s"
+                                      % (p, ", ".join(BUILT_OBJECT_PROPS)))
+        names += ["centroid-0", "centroid-1"] if p == "centroid" else [p]
+    return names
+
+
+def fiber_object_props(labels, fov, object_properties=FIBER_OBJECT_PROPS):
+    """The ``regionprops_table`` step of ``segment_fibers``: one row per non-zero label of a ``[H, W]`` label plane,
+    labels ascending -- ``fov`` first, then the properties in list order with ``centroid`` as ``centroid-0``,
+    ``centroid-1``.  An object is every pixel of one label, of any size.  An all-background plane gives an empty frame
+    with these columns; a property outside the built ones raises NotImplementedError."""
+    names = _object_columns(object_properties)
+    raw = _region_raw_device(_as_label_plane(labels, "labels"))
+    raw.setdefault("hull", np.zeros((np.asarray(raw["keys"]).size, 4), dtype=np.int64))   # no convex columns here
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cols = rpe.morphology(raw, orientation=True)
+    cols["label"] = np.asarray(raw["keys"], dtype=np.int64)
+    table = pd.DataFrame({name: cols[name] for name in names}, columns=names)
+    table.insert(0, FOV_ID, fov)
+    return table
+
+
+def fiber_objects(mask, fov, out_dir=None, min_fiber_size=15, object_properties=FIBER_OBJECT_PROPS, save_csv=False):
+    """The tail of ``segment_fibers`` from its binary ``segmentation`` on: ``ndi.label`` (4-connected), the components
+    under ``min_fiber_size`` pixels removed (``remove_small_objects``; labels are not renumbered, so gaps stay, as in
+    the reference), then :func:`fiber_object_props`.  With ``out_dir`` the labels are saved as
+    ``<fov>_fiber_labels.tiff`` (int32) and, with ``save_csv``, the table as ``fiber_object_table.csv`` as the
+    reference writes it.  Returns ``(table, labels)``."""
+    mask = np.asarray(mask)
+    if mask.ndim != 2 or mask.size == 0:
+        raise ValueError("mask must be a non-empty [H, W] array, got shape %s" % (mask.shape,))
+    _object_columns(object_properties)      # refuse an unbuilt property before any work
+    if out_dir is not None:
+        validate_paths(out_dir)
+    labels = _label_and_filter_device(mask, int(min_fiber_size))
+    if out_dir is not None:
+        image_io.write_image(os.path.join(out_dir, f"{fov}{_LABELS_SUFFIX}"), labels)
+    table = fiber_object_props(labels, fov, object_properties)
+    if save_csv:
+        if out_dir is None:
+            raise ValueError("save_csv needs out_dir")
+        table.to_csv(os.path.join(out_dir, "fiber_object_table.csv"))
+    return table, labels
+
+
+def fiber_object_table_from_labels(fibseg_dir, fovs=None, csv_compression: Optional[Dict[str, str]] = None):
+    """The fibre object table of a cohort from the ``<fov>_fiber_labels.tiff`` files of ``fibseg_dir`` (every such file
+    in natural order, or those of ``fovs``): one :func:`fiber_object_props` per FOV, stacked, with the alignment score
+    of :func:`calculate_fiber_alignment` (default k and threshold) as the last column, returned and written to
+    ``fiber_object_table.csv`` without the index -- the table ``run_fiber_segmentation`` leaves behind.  A cohort
+    without a single fibre gives the empty table with the same columns."""
+    validate_paths(fibseg_dir)
+    if fovs is None:
+        fovs = natsorted(f[:-len(_LABELS_SUFFIX)] for f in list_files(fibseg_dir, substrs=_LABELS_SUFFIX)
+                         if f.endswith(_LABELS_SUFFIX))
+    else:
+        fovs = [fovs] if isinstance(fovs, str) else list(fovs)
+        validate_paths([os.path.join(fibseg_dir, fov + _LABELS_SUFFIX) for fov in fovs])
+    if len(fovs) == 0:
+        raise ValueError("no %s files in %s" % ("<fov>" + _LABELS_SUFFIX, fibseg_dir))
+    per_fov = (fiber_object_props(image_io.read_image(os.path.join(fibseg_dir, fov + _LABELS_SUFFIX)), fov) for fov in fovs)
+    scored = calculate_fiber_alignment(pd.concat(list(per_fov)))
+    scored.to_csv(os.path.join(fibseg_dir, "fiber_object_table.csv"), index=False, compression=csv_compression)
+    return scored
+
+
+# ---- alignment ------------------------------------------------------------------------------------------------------
+def _rank_order_sums(terms: np.ndarray, counts: np.ndarray) -> np.ndarray:
+    """Per row of ``terms`` [m, k], the sum of its first ``counts[i]`` entries in the order numpy sums a contiguous
+    float64 vector of that many elements (a fold below 8, its pairwise rule from 8 on): rows are grouped by count and
+    every group is reduced along its contiguous last axis."""
+    out = np.zeros(terms.shape[0], dtype=np.float64)
+    for c in np.unique(counts):
+        if c > 0:
+            rows = counts == c
+            out[rows] = np.add.reduce(np.ascontiguousarray(terms[rows, :c]), axis=1)
+    return out
+
+
+def calculate_fiber_alignment(fiber_object_table, k=4, axis_thresh=2):
+    """The reference's alignment score, appended as ``alignment_score`` by a left merge on the shared columns: for every
+    fibre with ``major_axis_length / minor_axis_length >= axis_thresh`` (numpy's division: x / 0 = inf is kept, 0 / 0
+    is not), ``sqrt(sum (theta_j - theta_i)^2) / k`` over its k nearest such fibres j of the same FOV by centroid
+    distance.  The neighbours of the whole table come from one pxsom_nearest_indices launch; the sum runs in rank order
+    as numpy sums the reference's vector, so the scores are the reference's bits.  A fibre with m < k neighbours sums m
+    terms and still divides by k (a FOV's only fibre scores 0.0); the other fibres get NaN.
+
+    Where distances tie inside the first k + 1 ranks of a row the reference's ``argsort()[1 : 1 + k]`` is an unstable
+    sort's choice, and with a fibre on the same centroid it may keep the fibre itself in place of the other: that is
+    not reproducible.  Here ties go to the earlier row of the table and a fibre is never its own neighbour.  ``k`` is
+    limited to 1 .. 32 (the device route); a table without rows comes back with an empty ``alignment_score`` column,
+    where the reference's ``pd.concat`` raises."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1, got %d" % k)
+    if k > NEAREST_MAX_K:
+        raise NotImplementedError("k=%d: the device route keeps the k nearest fibres in registers, k <= %d"
+                                  % (k, NEAREST_MAX_K))
+    table = fiber_object_table
+    fov_values = np.asarray(table[FOV_ID])
+    fovs, codes = np.unique(fov_values, return_inverse=True) if len(table) else (np.array([]), np.zeros(0, np.int64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        keep = (table["major_axis_length"].values / table["minor_axis_length"].values) >= axis_thresh
+    rows = np.flatnonzero(keep)
+    rows = rows[np.argsort(codes[rows], kind="stable")]                 # FOV by FOV in np.unique's order, table order inside
+    seg = np.concatenate([[0], np.cumsum(np.bincount(codes[rows], minlength=len(fovs)))]).astype(np.int64)
+    xy = np.stack([table["centroid-0"].values[rows], table["centroid-1"].values[rows]], axis=1).astype(np.float64)
+    theta = np.asarray(table["orientation"].values[rows], dtype=np.float64)
+    if len(rows):
+        idx = np.asarray(_nearest_indices_device(xy, seg, k)).reshape(len(rows), k)
+        found = idx >= 0
+        diff = np.where(found, theta[np.where(found, idx, 0)] - theta[:, None], 0.0)
+        scores = np.sqrt(_rank_order_sums(np.square(diff), found.sum(axis=1))) / k
+    else:
+        scores = np.zeros(0, dtype=np.float64)
+    alignment_data = pd.DataFrame({FOV_ID: fov_values[rows], "label": table["label"].values[rows],
+                                   "alignment_score": scores})
+    if len(table) == 0:
+        alignment_data = alignment_data.astype({FOV_ID: table[FOV_ID].dtype, "label": table["label"].dtype})
+    return table.merge(alignment_data, "left")
+
+
+# ---- densities and summaries (host) ---------------------------------------------------------------------------------
+# Written against the contract of the reference's functions -- their arguments, columns, file names, NaN rules and error
+# text -- and the g26 fixture: fibres are binned into tiles once and every statistic is a grouped reduction over the bins.
+_STAT_COLUMNS = ["pixel_density", "fiber_density"]
+
+
+def _percent_of(count, total_pixels):
+    """``count / total_pixels`` as a percentage, the quotient first (the rounding order the fixture records)."""
+    return count / total_pixels * 100
+
+
+def calculate_density(fov_fiber_table, total_pixels):
+    """``(pixel_density, fiber_density)`` of a table of fibres over an area of ``total_pixels``, in percent: the fibres'
+    summed ``area`` per pixel, and the number of distinct ``label`` values per pixel."""
+    covered = fov_fiber_table["area"].to_numpy().sum()
+    distinct = fov_fiber_table["label"].nunique()
+    return _percent_of(covered, total_pixels), _percent_of(distinct, total_pixels)
+
+
+def _tile_bins(centroids, tiles_per_side, tile_length):
+    """The tile index along one axis of every centroid, -1 outside ``[0, tiles_per_side * tile_length)`` (NaN too):
+    ``edge[i] <= c < edge[i + 1]`` decided by comparison with the integer edges, never by a division of the centroid."""
+    edges = np.arange(tiles_per_side + 1) * tile_length
+    bins = np.searchsorted(edges, np.asarray(centroids, dtype=np.float64), side="right") - 1
+    return np.where((bins >= 0) & (bins < tiles_per_side), bins, -1)
+
+
+def generate_tile_stats(fov_table, fov_fiber_img, fov_length, tile_length, min_fiber_num, save_dir, save_tiles):
+    """Tile statistics of one FOV: one row per ``tile_length`` square of an image of side ``fov_length``, row by row of
+    tiles (``fov``, ``tile_y``, ``tile_x``), over the fibres whose centroid lies in the square: ``pixel_density`` and
+    ``fiber_density`` (:func:`calculate_density` over the tile's area), ``avg_alignment_score`` (the mean of the scores
+    that are not NaN) and ``avg_<property>`` for the six object properties.  A tile with fewer than ``min_fiber_num``
+    fibres is NaN throughout, and its alignment mean also when fewer than that many of its fibres are scored.
+    ``save_tiles`` writes every tile of ``fov_fiber_img``, binarised, to ``<save_dir>/<fov>/tile_<y>,<x>.tiff``; the
+    caller's image is left as it is (the reference binarises it in place, through the view it crops)."""
+    if len(fov_table) == 0:
+        raise ValueError("generate_tile_stats needs at least one fibre to name the FOV")
+    fov = fov_table[FOV_ID].iloc[0]
+    per_side = int(fov_length // tile_length)
+    n_tiles = per_side * per_side
+    by, bx = (_tile_bins(fov_table[c].to_numpy(), per_side, tile_length) for c in ("centroid-0", "centroid-1"))
+    inside = (by >= 0) & (bx >= 0)
+    fibres = fov_table[inside].assign(_tile=(by * per_side + bx)[inside])
+    tiles = fibres.groupby("_tile")
+    every = pd.RangeIndex(n_tiles)
+
+    members = tiles.size().reindex(every, fill_value=0)
+    scored = tiles["alignment_score"].count().reindex(every, fill_value=0)          # NaN is not counted
+    enough = (members >= min_fiber_num).to_numpy()
+    area = tiles["area"].sum().reindex(every, fill_value=0).to_numpy()
+    distinct = tiles["label"].nunique().reindex(every, fill_value=0).to_numpy()
+    out = pd.DataFrame({FOV_ID: [fov] * n_tiles,
+                        "tile_y": np.repeat(np.arange(per_side), per_side) * tile_length,
+                        "tile_x": np.tile(np.arange(per_side), per_side) * tile_length})
+    out["pixel_density"] = np.where(enough, _percent_of(area, tile_length ** 2), np.nan)
+    out["fiber_density"] = np.where(enough, _percent_of(distinct, tile_length ** 2), np.nan)
+    score_mean = tiles["alignment_score"].mean().reindex(every).to_numpy(dtype=np.float64)
+    out["avg_alignment_score"] = np.where(enough & (scored >= min_fiber_num).to_numpy(), score_mean, np.nan)
+    means = tiles[_TILE_PROPERTIES].mean().reindex(every)
+    for name in _TILE_PROPERTIES:
+        out["avg_" + name] = np.where(enough, means[name].to_numpy(dtype=np.float64), np.nan)
+
+    if save_tiles:
+        folder = os.path.join(save_dir, fov)
+        os.makedirs(folder, exist_ok=True)
+        plane = np.asarray(fov_fiber_img)
+        for y, x in zip(out["tile_y"], out["tile_x"]):
+            binary = (plane[y:y + tile_length, x:x + tile_length] > 0).astype(plane.dtype)
+            image_io.write_image(os.path.join(folder, "tile_%d,%d.tiff" % (y, x)), binary)
+    return out
+
+
+def generate_summary_stats(fiber_object_table, fibseg_dir, tile_length=512, min_fiber_num=5, save_tiles=False):
+    """FOV and tile summaries of a fibre object table.  ``fov_stats``: per FOV (sorted) the two densities over the whole
+    image -- its side read from ``<fov>_fiber_labels.tiff`` in ``fibseg_dir`` -- and ``avg_<column>`` for the six object
+    properties and ``alignment_score`` (NaN skipped), written to ``fiber_stats_table.csv``.  ``tile_stats``:
+    :func:`generate_tile_stats` of every FOV, stacked, written to
+    ``tile_stats_<tile_length>/fiber_stats_table-tile_<tile_length>.csv``.  ``tile_length`` must divide 1024."""
+    validate_paths(fibseg_dir)
+    if 1024 % tile_length != 0:
+        raise ValueError("Tile length must be a factor of the minimum image size.")
+    tile_dir = os.path.join(fibseg_dir, "tile_stats_%s" % tile_length)
+    columns = _TILE_PROPERTIES + ["alignment_score"]
+    fov_rows, tile_frames = [], []
+    for fov, fibres in fiber_object_table.groupby(FOV_ID, sort=True):
+        plane = _as_label_plane(image_io.read_image(os.path.join(fibseg_dir, fov + _LABELS_SUFFIX)), fov)
+        side = plane.shape[0]
+        row = dict(zip([FOV_ID] + _STAT_COLUMNS, (fov,) + calculate_density(fibres, side ** 2)))
+        row.update(("avg_" + name, value) for name, value in fibres[columns].mean().items())
+        fov_rows.append(row)
+        tile_frames.append(generate_tile_stats(fibres, plane, side, tile_length, min_fiber_num, tile_dir, save_tiles))
+    fov_stats = pd.DataFrame(fov_rows, columns=[FOV_ID] + _STAT_COLUMNS + ["avg_" + name for name in columns])
+    tile_stats = pd.concat(tile_frames)
+    os.makedirs(tile_dir, exist_ok=True)
+    fov_stats.to_csv(os.path.join(fibseg_dir, "fiber_stats_table.csv"), index=False)
+    tile_stats.to_csv(os.path.join(tile_dir, "fiber_stats_table-tile_%s.csv" % tile_length), index=False)
+    return fov_stats, tile_stats
+
+
+# ---- the entries whose front half is not built --------------------------------------------------------------------------
+def _refuse(entry, folders, channel_folder, fiber_channel):
+    """What the three entries below share: every folder must exist, ``fiber_channel`` must name an image file of
+    ``channel_folder()`` (None: nothing to look up), and then the entry is refused."""
+    validate_paths(list(folders))
+    if channel_folder is not None:
+        channels = remove_file_extensions(list_files(channel_folder()))
+        verify_in_list(fiber_channel=[fiber_channel], all_channels=channels)
+    raise NotImplementedError(entry + ": " + _UNBUILT)
+
+
+def plot_fiber_segmentation_steps(data_dir, fov_name, fiber_channel, img_sub_folder=None, blur=2,
+                                  contrast_scaling_divisor=128, fiber_widths=range(1, 10, 2), ridge_cutoff=0.1,
+                                  sobel_blur=1, min_fiber_size=15, img_cmap="bone", labels_cmap="cool"):
+    """The reference's signature.  ``data_dir`` must exist and hold ``fiber_channel`` for ``fov_name``
+    (FileNotFoundError, ValueError); then NotImplementedError: the steps it would plot are not built."""
+    _refuse("plot_fiber_segmentation_steps", [data_dir],
+            lambda: os.path.join(data_dir, fov_name, img_sub_folder or ""), fiber_channel)
+
+
+def run_fiber_segmentation(data_dir, fiber_channel, out_dir, img_sub_folder=None,
+                           csv_compression: Optional[Dict[str, str]] = None, **kwargs):
+    """The reference's signature.  Both folders must exist and the first FOV of ``data_dir`` (natural order) must hold
+    ``fiber_channel`` (FileNotFoundError, ValueError); then NotImplementedError naming the stages that are not built."""
+    _refuse("run_fiber_segmentation", [data_dir, out_dir],
+            lambda: os.path.join(data_dir, natsorted(list_folders(data_dir))[0], img_sub_folder or ""), fiber_channel)
+
+
+def segment_fibers(data_xr, fiber_channel, out_dir, fov, blur=2, contrast_scaling_divisor=128,
+                   fiber_widths=range(1, 10, 2), ridge_cutoff=0.1, sobel_blur=1, min_fiber_size=15,
+                   object_properties=FIBER_OBJECT_PROPS, save_csv=True, debug=False):
+    """The reference's signature; ``out_dir`` must exist and the properties must be built ones; then
+    NotImplementedError naming the stages that are not built."""
+    _object_columns(object_properties)
+    _refuse("segment_fibers", [out_dir], None, fiber_channel)

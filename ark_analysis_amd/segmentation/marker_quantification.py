@@ -12,7 +12,8 @@ two transforms (``size_norm``, ``arcsinh``) and the frame layout stay on the hos
 one pxsom_region_shape and one pxsom_region_hull pass per compartment: raw integers from the device,
 the float columns from regionprops_extraction on the host; skimage is taken by its documented algorithms and parity
 with skimage itself is not pinned.  The bare call (``fast_extraction=False`` with none of the three lists named) keeps
-raising NotImplementedError, as do MIBItiff inputs and a base property outside the eight built ones;
+raising NotImplementedError, as do MIBItiff inputs and a base property outside the built ones
+(regionprops_extraction.BUILT_BASE; ``orientation`` and ``euler_number`` came with DESIGN.md K23);
 ``create_marker_count_matrices`` / ``compute_marker_counts`` are not mirrored (they take and return xarray).
 ``split_large_nuclei=True`` re-cuts the nuclear plane at the cell borders on the device before anything nuclear is
 computed (segmentation_utils.split_large_nuclei); it needs ``nuclear_counts=True``."""
@@ -70,21 +71,26 @@ def _quantify(image_dev, seg, mode, threshold, nuc=None) -> dict:
     return out
 
 
-def _region_raw(seg, q=None, **thresholds) -> dict:
+def _region_raw(seg, q=None, euler=False, **thresholds) -> dict:
     """pxsom_region_shape and pxsom_region_hull over one compartment: a host label image in, the raw integers of
     som_device.region_props out as host arrays, the cells the device leaves out filled by the host route.  With the
     result ``q`` of :func:`_quantify` over the same label image, its uploaded image, key table, counts, sums and boxes
-    are reused: no second upload, no second key table, and the shape pass skips the statistics atomics."""
+    are reused: no second upload, no second key table, and the shape pass skips the statistics atomics.  ``euler`` adds
+    ``euler`` (one pxsom_region_euler pass), which only the ``euler_number`` column needs."""
     import torch
     from .. import _capi, som_device
     kept = q.get("_device") if q is not None else None
     if kept is not None:
-        got = som_device.region_props(kept["seg"], keys=kept["keys"], count=kept["count"], sums=kept["sums"],
+        seg_dev = kept["seg"]
+        got = som_device.region_props(seg_dev, keys=kept["keys"], count=kept["count"], sums=kept["sums"],
                                       bbox=kept["bbox"], **thresholds)
     else:
         dev = _capi.require_gpu()
         a = np.ascontiguousarray(seg)
-        got = som_device.region_props(torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev), **thresholds)
+        seg_dev = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+        got = som_device.region_props(seg_dev, **thresholds)
+    if euler:
+        got["euler"] = som_device.region_euler(seg_dev, keys=got["keys"])
     raw = {k: v.cpu().numpy() for k, v in got.items()}
     return rpe.fill_left_out(raw, seg, **thresholds)
 
@@ -142,11 +148,11 @@ def _morph_block(seg, q, props):
     """The morphology columns of one compartment as a float64 [n, len(names)] block in the table's order
     (regionprops_extraction.table_names), rows in the order of the quantify result ``q``."""
     base, single, _, thresholds = props
-    raw = _region_raw(seg, q, **thresholds)
+    raw = _region_raw(seg, q, euler="euler_number" in base, **thresholds)
     if not np.array_equal(np.asarray(raw["keys"], dtype=np.int64), np.asarray(q["keys"], dtype=np.int64)):
         raise RuntimeError("generate_cell_table: the morphology pass and the signal pass name different cells")
-    cols = rpe.morphology(raw)
     names = rpe.table_names(base, single)
+    cols = rpe.morphology(raw, orientation="orientation" in names)
     block = np.zeros((np.asarray(raw["keys"]).size, len(names)), dtype=np.float64)
     for j, name in enumerate(names):
         block[:, j] = cols[name]
@@ -160,7 +166,8 @@ def get_single_compartment_props(segmentation_labels, regionprops_base, regionpr
     gives an empty frame with the same columns."""
     base, single, _ = rpe.resolve_lists(regionprops_base, regionprops_single_comp, [])
     seg = _as_label_plane(segmentation_labels, "segmentation_labels")
-    return rpe.props_frame(_region_raw(seg, **rpe.concavity_thresholds(**kwargs)), base, single)
+    return rpe.props_frame(_region_raw(seg, euler="euler_number" in base, **rpe.concavity_thresholds(**kwargs)), base,
+                           single)
 
 
 def _fov_frames(fov, image_dev, channels, segs, mask_types, add_underscore, nuclear_counts, mode, threshold,

@@ -24,7 +24,7 @@ REGIONPROPS_SINGLE_COMP = ["major_minor_axis_ratio", "perim_square_over_area", "
 REGIONPROPS_MULTI_COMP = ["nc_ratio"]
 REGIONPROPS_FUNCTION_NAMES = REGIONPROPS_SINGLE_COMP + REGIONPROPS_MULTI_COMP                   # REGIONPROPS_FUNCTION's keys
 BUILT_BASE = ("area", "eccentricity", "major_axis_length", "minor_axis_length", "perimeter", "centroid",
-              "convex_area", "equivalent_diameter")
+              "convex_area", "equivalent_diameter", "orientation", "euler_number")
 CONCAVITY_DEFAULTS = {"small_concavity_minimum": 10, "max_compactness": 60, "large_concavity_minimum": 150}
 MAX_SIDE = 64          # the device route of the hull ends at a 64 x 64 bounding box
 
@@ -180,7 +180,40 @@ def host_hull(mask, r0=0, c0=0, **thresholds):
     return area, sum_r, sum_c, count_concavities(convex & ~mask, **concavity_thresholds(**thresholds))
 
 
-def host_raw(seg, keys=None, **thresholds):
+# 4 E's term of the four bits (top left, top right, bottom left, bottom right) = (bit 0 .. bit 3) of one label in one
+# 2 x 2 window: one bit +1, three bits -1, two bits on a diagonal -2
+_QUAD_TERM = np.array([0, 1, 1, 0, 1, 0, -2, -1, 1, -2, 0, -1, 0, -1, -1, 0], dtype=np.int64)
+
+
+def euler_numbers(seg, keys):
+    """Per key, the Euler number of ``seg == key`` under 8-connectivity (objects minus holes, the plane padded by a zero
+    border) by bit quads, as pxsom_region_euler states it: [n] int64."""
+    seg = np.asarray(seg)
+    keys = np.asarray(keys, dtype=np.int64)
+    total = np.zeros(keys.size, dtype=np.int64)
+    if keys.size == 0:
+        return total
+    p = np.zeros((seg.shape[0] + 2, seg.shape[1] + 2), dtype=np.int64)
+    p[1:-1, 1:-1] = seg
+    quad = [p[:-1, :-1], p[:-1, 1:], p[1:, :-1], p[1:, 1:]]
+    mixed = (quad[0] != quad[1]) | (quad[0] != quad[2]) | (quad[0] != quad[3])
+    quad = [q[mixed] for q in quad]
+    for i, lab in enumerate(quad):
+        first = lab != 0                                  # every distinct label once, at its first position
+        for earlier in quad[:i]:
+            first &= earlier != lab
+        bits = np.zeros(lab.size, dtype=np.int64)
+        for j, other in enumerate(quad):
+            bits |= (other == lab).astype(np.int64) << j
+        pos = np.minimum(np.searchsorted(keys, lab), keys.size - 1)
+        named = first & (keys[pos] == lab)
+        np.add.at(total, pos[named], _QUAD_TERM[bits[named]])
+    if np.any(total % 4):
+        raise AssertionError("bit-quad totals must be multiples of 4")
+    return total // 4
+
+
+def host_raw(seg, keys=None, euler=False, **thresholds):
     """The contract of som_device.region_props as host arrays, computed in numpy for every cell (``left_out`` all 0):
     the statement the CPU tests put in the device's place, and the route of :func:`fill_left_out`."""
     seg = np.asarray(seg)
@@ -192,6 +225,8 @@ def host_raw(seg, keys=None, **thresholds):
     out = {"keys": keys.astype(np.int32), "count": np.zeros(n, np.int64), "sums": np.zeros((n, 2), np.int64),
            "bbox": np.tile(np.array([2**31 - 1, -1, 2**31 - 1, -1], np.int32), (n, 1)),
            "shape": np.zeros((n, 6), np.int64), "hull": np.zeros((n, 4), np.int64), "left_out": np.zeros(n, np.int32)}
+    if euler:           # som_device.region_euler's integers, which only the euler_number column needs
+        out["euler"] = euler_numbers(seg, keys)
     if n == 0:
         return out
     from scipy import ndimage
@@ -229,8 +264,10 @@ def _ints(a):
     return [int(v) for v in np.asarray(a).ravel()]
 
 
-def morphology(raw):
-    """Every built column (base and single-compartment) of the cells of ``raw`` as a dict of arrays.  The central second
+def morphology(raw, orientation=False):
+    """Every built column (base and single-compartment) of the cells of ``raw`` as a dict of arrays; ``euler_number``
+    when ``raw`` holds ``euler`` (the integers of som_device.region_euler) and ``orientation`` on request (one atan2 per
+    cell, which only that column needs).  The central second
     moments come from exact integer numerators (n sum r^2 - (sum r)^2 and its siblings, Python integers) with one
     rounding per quotient; the eigenvalues of the inertia tensor [[mu02, -mu11], [-mu11, mu20]] / n are l1 from the
     trace and the discriminant and l2 = det / l1, the determinant again one exact integer quotient."""
@@ -243,6 +280,7 @@ def morphology(raw):
     d = np.zeros(m)
     b = np.zeros(m)
     det = np.zeros(m)
+    theta = np.zeros(m)
     for i in range(m):
         ni, sr, sc = n[i], int(sums[i, 0]), int(sums[i, 1])
         if ni == 0:
@@ -250,6 +288,14 @@ def morphology(raw):
         srr, scc, src = int(shape[i, 0]), int(shape[i, 1]), int(shape[i, 2])
         num_a, num_d, num_b = ni * scc - sc * sc, ni * srr - sr * sr, ni * src - sr * sc
         a[i], d[i], b[i] = num_a / (ni * ni), num_d / (ni * ni), -num_b / (ni * ni)
+        # skimage 0.19 RegionProperties.orientation over the inertia tensor [[a, b], [b, d]], b by float negation: a zero
+        # mu11 gives -0.0, the sign skimage's -mu11 / mu00 has (math.atan2: one libm call per cell, no SIMD variant)
+        if orientation:
+            b_neg = -(num_b / (ni * ni))
+            if a[i] == d[i]:
+                theta[i] = -math.pi / 4 if b_neg < 0 else math.pi / 4
+            else:
+                theta[i] = 0.5 * math.atan2(-2 * b_neg, d[i] - a[i])
         det[i] = (num_a * num_d - num_b * num_b) / (ni ** 4)
     area = np.asarray(n, dtype=np.float64)
     l1 = np.maximum((a + d) / 2 + np.sqrt(((a - d) / 2) ** 2 + b * b), 0.0)
@@ -276,16 +322,20 @@ def morphology(raw):
             "num_concavities": hull[:, 3].copy(),
             "eigenvalues": np.stack([l1, l2], axis=1),
         }
+    if orientation:
+        out["orientation"] = theta
+    if "euler" in raw:
+        out["euler_number"] = np.asarray(raw["euler"], dtype=np.int64).copy()
     return out
 
 
 def props_frame(raw, base, single):
     """get_single_compartment_props' frame (without ``coords``): the base properties in list order, ``centroid`` as
     ``centroid-0`` and ``centroid-1`` in its place, then the single-compartment ones; one row per cell, labels ascending."""
-    cols = morphology(raw)
-    cols["label"] = np.asarray(raw["keys"], dtype=np.int64)
     names = []
     for p in base:
         names += ["centroid-0", "centroid-1"] if p == "centroid" else [p]
     names += list(single)
+    cols = morphology(raw, orientation="orientation" in names)
+    cols["label"] = np.asarray(raw["keys"], dtype=np.int64)
     return pd.DataFrame({name: cols[name] for name in names}, columns=names)

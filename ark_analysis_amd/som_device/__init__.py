@@ -27,9 +27,10 @@ from .planes import (BIN_LEVEL, BIN_LOCAL, BIN_POSITIVE, BLUR_MAX_RADIUS, BLUR_M
                      segmask_table, segmentation_mask, zero_by_segmentation, _blur_plane, _region_tables)
 from .cells import (CELLQUANT_FORCE_SEARCH, CELLQUANT_IMAGE_DTYPES, CELLQUANT_MODES, CELLQUANT_NUC_CAPACITY,
                     CONCAVITY_DEFAULTS, NUCSPLIT_FORCE_SEARCH, REGION_FORCE_SEARCH, REGION_MAX_SIDE, cell_quantify,
-                    choose_splits, label_keys, nuclear_overlaps, region_props, split_large_nuclei, split_nuclei_apply,
-                    _split_planes)
-from .spatial import (CLOSE_PAIR_MAX_SETS, NEAREST_MAX_K, _S_ZERO, close_pair_counts, nearest_type_means, neighbor_counts,
+                    choose_splits, label_keys, nuclear_overlaps, region_euler, region_moments, region_props,
+                    split_large_nuclei, split_nuclei_apply, _region_keys, _split_planes)
+from .spatial import (CLOSE_PAIR_MAX_SETS, NEAREST_MAX_K, _S_ZERO, close_pair_counts, nearest_indices, nearest_type_means,
+                      neighbor_counts,
                       neighbor_thresholds, _cell_args, _cells_sorted_by_type, _check_offsets, _nearest_s_zero,
                       _smallest_double)
 from .clustering import (KMEANS_MAX_D, KMEANS_MAX_K, KMEANS_MAX_PROBLEMS, SILHOUETTE_MAX_D, SILHOUETTE_MAX_K,

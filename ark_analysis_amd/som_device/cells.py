@@ -161,6 +161,58 @@ def region_props(seg: torch.Tensor, keys: Optional[torch.Tensor] = None, count: 
     return out
 
 
+def _region_keys(seg: torch.Tensor, keys: Optional[torch.Tensor]):
+    """``(h, w, ld, keys, n, key_min, key_max)`` of a label image and its key table (default :func:`label_keys`)."""
+    h, w, ld = _label_image(seg, "seg")
+    if keys is None:
+        keys = label_keys(seg)
+    kmin, kmax = _key_range(keys)
+    n = keys.numel()
+    if n and kmin <= 0:
+        raise ValueError("keys must be positive")
+    return h, w, ld, keys, n, kmin, kmax
+
+
+def region_moments(seg: torch.Tensor, keys: Optional[torch.Tensor] = None, force_search: bool = False) -> dict:
+    """:func:`region_props` without the hull launch, for objects of any size (pxsom_region_shape streams the image and
+    has no bounding-box limit; only the hull kernel has one): a dict of HBM tensors ``keys``, ``count`` [n] int64,
+    ``sums`` [n, 2] int64, ``bbox`` [n, 4] int32 and ``shape`` [n, 6] int64, as :func:`region_props` describes them."""
+    # the key, workspace and pxsom_region_shape half of region_props, which stays as it was: keep the two in step
+    h, w, ld, keys, n, kmin, kmax = _region_keys(seg, keys)
+    dev = seg.device
+    out = {"keys": keys,
+           "count": torch.empty(n, dtype=torch.int64, device=dev),
+           "sums": torch.empty((n, 2), dtype=torch.int64, device=dev),
+           "bbox": torch.empty((n, 4), dtype=torch.int32, device=dev),
+           "shape": torch.empty((n, 6), dtype=torch.int64, device=dev)}
+    flags = REGION_FORCE_SEARCH if force_search else 0
+    wsb = _capi.lib().pxsom_region_shape_workspace_bytes(n, kmin, kmax, flags)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    _capi.call("pxsom_region_shape", seg.data_ptr(), SEG_DTYPES[seg.dtype], ld, h, w, keys.data_ptr() if n else None, n,
+               kmin, kmax, out["shape"].data_ptr(), out["count"].data_ptr(), out["sums"].data_ptr(),
+               out["bbox"].data_ptr(), ws.data_ptr(), wsb, flags, _capi.stream_ptr())
+    return out
+
+
+def region_euler(seg: torch.Tensor, keys: Optional[torch.Tensor] = None, force_search: bool = False,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pxsom_region_euler: per key (default :func:`label_keys` of ``seg``) the Euler number of ``seg == key`` under
+    8-connectivity -- objects minus holes, the plane padded by a zero border -- as an ``[n]`` int64 HBM vector (``out``
+    when given).  ``seg`` as for :func:`region_props`; ``force_search`` takes the binary-search route of the key table."""
+    h, w, ld, keys, n, kmin, kmax = _region_keys(seg, keys)
+    dev = seg.device
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (n,) or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous [n] int64 HBM vector")
+    flags = REGION_FORCE_SEARCH if force_search else 0
+    wsb = _capi.lib().pxsom_region_euler_workspace_bytes(n, kmin, kmax, flags)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    _capi.call("pxsom_region_euler", seg.data_ptr(), SEG_DTYPES[seg.dtype], ld, h, w, keys.data_ptr() if n else None, n,
+               kmin, kmax, out.data_ptr(), ws.data_ptr(), wsb, flags, _capi.stream_ptr())
+    return out
+
+
 # pxsom_nuclear_overlaps / pxsom_split_apply (K21)
 NUCSPLIT_FORCE_SEARCH = 1
 

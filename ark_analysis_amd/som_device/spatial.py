@@ -1,6 +1,7 @@
-"""Cell geometry: the neighbourhood matrix (K13), close-pair counts (K20), nearest-type distances (K14)."""
+"""Cell geometry: the neighbourhood matrix (K13), close-pair counts (K20), nearest-type distances (K14), nearest
+points (K23)."""
 import operator
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -179,3 +180,28 @@ def nearest_type_means(xy: torch.Tensor, types: torch.Tensor, seg: torch.Tensor,
                s_zero, sorted_means.data_ptr(), _capi.stream_ptr())
     means[order] = sorted_means
     return means
+
+
+# ---- nearest points (K23) -------------------------------------------------------------------------------------------
+def nearest_indices(xy: torch.Tensor, seg: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pxsom_nearest_indices: ``idx[i]`` (``[n, k]`` int32, HBM; ``out`` when given) = the positions in ``0 .. n - 1`` of
+    the k nearest other points of point i's FOV, nearest first, ordered by ``s = fl(fl(dx * dx) + fl(dy * dy))`` in
+    binary64 with ties to the lower position; i is excluded by identity, so a point on i's coordinates is a neighbour.
+    A FOV with fewer than k + 1 points leaves the tail of its rows at -1.  ``xy`` [n, 2] float64 and finite, ``seg``
+    [F + 1] int64 offsets as for :func:`neighbor_counts`; the rows need no order inside a FOV.  ``1 <= k <= 32``."""
+    k = operator.index(k)
+    if not 1 <= k <= NEAREST_MAX_K:
+        raise ValueError("k must lie in 1 .. %d (the device route keeps the k nearest in registers), got %d"
+                         % (NEAREST_MAX_K, k))
+    n, dev, seg, n_fovs = _cell_args(xy, seg, lambda n, dev: None)
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (n, k) or out.device != dev or not out.is_contiguous():
+        raise ValueError("out must be a contiguous [n, k] int32 HBM tensor on xy's device")
+    if not _check_offsets(seg, n, torch.isfinite(xy).all())[0]:
+        raise ValueError("xy must be finite")
+    if n == 0:
+        return out
+    xy = xy.contiguous()
+    _capi.call("pxsom_nearest_indices", xy.data_ptr(), seg.data_ptr(), n_fovs, n, k, out.data_ptr(), _capi.stream_ptr())
+    return out

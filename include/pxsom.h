@@ -967,6 +967,35 @@ int pxsom_split_apply(const void *cell_dev, int cell_dtype, int64_t ldc, const v
                       const int64_t *cell_value_dev, const int64_t *nuc_value_dev, void *out_dev, int64_t ldo,
                       void *workspace_dev, size_t workspace_bytes, int flags, void *stream);
 
+/* ---- fibre object tables: per-label Euler numbers and k nearest points (K23) -----------------------------------------
+ * reference: ark/segmentation/fiber_segmentation.py -- regionprops_table's euler_number column and the
+ * cdist(...).argsort()[1 : 1 + k] neighbours of calculate_fiber_alignment.  Symbols added under ABI 9, none changed.
+ *
+ * pxsom_region_euler: per key i, euler_dev[i] (int64, every entry written) = the Euler number of (seg == keys[i]) under
+ * 8-connectivity, objects minus holes, the plane padded by a zero border -- by bit quads: over every 2 x 2 window of the
+ * padded plane and every distinct non-zero label l in it, the four bits (window == l) give +1 for one bit set, -1 for
+ * three, -2 for two on a diagonal and 0 otherwise; the total is 4 E.  seg_dev, seg_dtype, ld, keys_dev, key_min, key_max,
+ * flags and the workspace rule (pxsom_region_euler_workspace_bytes): as for pxsom_region_shape; a label past int32 is
+ * background; h and w at most 2^31 - 129.  One streaming pass, integer atomics only: the same input gives the same bits.
+ *
+ * pxsom_nearest_indices:
+ *   xy_dev    [n, 2] binary64 points, 16-byte aligned; any order inside a FOV
+ *   seg_dev   [n_fovs + 1] int64 offsets, as for pxsom_neighbor_counts
+ *   k         1 .. 32 (the device route's limit: the k nearest live in registers)
+ *   idx_dev   [n, k] int32, every entry written: the positions in 0 .. n - 1 of the k nearest OTHER points of the row's
+ *             FOV, nearest first; -1 from the first entry the FOV has no point for, and for a row no FOV holds
+ * Order: s = fl(fl(dx * dx) + fl(dy * dy)) in binary64 without contraction, ties to the lower position.  Point i is
+ * excluded by identity, so a point on the same coordinates as i is a neighbour.  A candidate whose s is not below +inf
+ * (overflow, NaN) is never a neighbour.  No workspace; n <= 2^31 - 1.  Offsets are clamped to [0, n], so bad device-side
+ * input gives wrong rows, never a write outside idx_dev.  Bad sizes, k, null / misaligned pointers:
+ * PXSOM_ERR_INVALID_ARG before any HIP call. */
+size_t pxsom_region_euler_workspace_bytes(int64_t n_keys, int32_t key_min, int32_t key_max, int flags);
+int pxsom_region_euler(const void *seg_dev, int seg_dtype, int64_t ld, int h, int w, const int32_t *keys_dev,
+                       int64_t n_keys, int32_t key_min, int32_t key_max, int64_t *euler_dev, void *workspace_dev,
+                       size_t workspace_bytes, int flags, void *stream);
+int pxsom_nearest_indices(const double *xy_dev, const int64_t *seg_dev, int64_t n_fovs, int64_t n, int k,
+                          int32_t *idx_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
