@@ -154,6 +154,7 @@ SYMBOLS = {
     "pxsom_region_euler": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _sz,
                                   _i32, _vp]),
     "pxsom_nearest_indices": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "pxsom_neighborhood_sums": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _f64, _vp, _vp, _vp]),
 }
 
 _lib = None

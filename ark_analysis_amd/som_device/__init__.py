@@ -30,8 +30,8 @@ from .cells import (CELLQUANT_FORCE_SEARCH, CELLQUANT_IMAGE_DTYPES, CELLQUANT_MO
                     choose_splits, label_keys, nuclear_overlaps, region_euler, region_moments, region_props,
                     split_large_nuclei, split_nuclei_apply, _region_keys, _split_planes)
 from .spatial import (CLOSE_PAIR_MAX_SETS, NEAREST_MAX_K, _S_ZERO, close_pair_counts, nearest_indices, nearest_type_means,
-                      neighbor_counts,
-                      neighbor_thresholds, _cell_args, _cells_sorted_by_type, _check_offsets, _nearest_s_zero,
+                      neighbor_counts, neighbor_thresholds, neighborhood_sums, radius_threshold, _cell_args, _cells_sorted_by_type, _check_offsets, _nearest_s_zero,
                       _smallest_double)
 from .clustering import (KMEANS_MAX_D, KMEANS_MAX_K, KMEANS_MAX_PROBLEMS, SILHOUETTE_MAX_D, SILHOUETTE_MAX_K,
-                         kmeans_group_count, kmeans_lloyd, silhouette_samples, silhouette_scores, _kmeans_ks, _silhouette)
+                         kmeans_group_count, kmeans_lloyd, silhouette_samples, silhouette_scores, silhouette_sums, _kmeans_ks, _silhouette,
+                         _silhouette_call)

@@ -12,9 +12,10 @@ SILHOUETTE_MAX_D = 64   # pxsom_silhouette keeps a row in registers
 SILHOUETTE_MAX_K = 32
 
 
-def _silhouette(x: torch.Tensor, labels: torch.Tensor, n_clusters):
-    """The checks, the sort by label and the one pxsom_silhouette call behind :func:`silhouette_samples` and
-    :func:`silhouette_scores`: ``(samples [M, n], scores [M], single)``, ``single`` when ``labels`` came as ``[n]``."""
+def _silhouette_call(x: torch.Tensor, labels: torch.Tensor, n_clusters):
+    """The checks, the sort by label and the one pxsom_silhouette call behind :func:`silhouette_samples`,
+    :func:`silhouette_scores` and :func:`silhouette_sums`: ``(samples [M, n], scores [M], single, sums [M, n, k],
+    counts [M, k])``, ``single`` when ``labels`` came as ``[n]`` and k the largest of ``n_clusters``."""
     if x.dim() != 2 or x.dtype != torch.float64:
         raise ValueError("x must be an [n, d] float64 HBM tensor")
     n, d = x.shape
@@ -57,7 +58,21 @@ def _silhouette(x: torch.Tensor, labels: torch.Tensor, n_clusters):
     _capi.call("pxsom_silhouette", x.data_ptr(), n, d, labels32.data_ptr(), order.data_ptr(), n_labelings, k,
                counts.data_ptr(), sums.data_ptr(), samples.data_ptr(), scores.data_ptr(),
                _capi.stream_ptr())
-    return samples, scores, single
+    return samples, scores, single, sums, counts
+
+
+def _silhouette(x: torch.Tensor, labels: torch.Tensor, n_clusters):
+    """``(samples [M, n], scores [M], single)`` of :func:`_silhouette_call`."""
+    return _silhouette_call(x, labels, n_clusters)[:3]
+
+
+def silhouette_sums(x: torch.Tensor, labels: torch.Tensor, n_clusters):
+    """What pxsom_silhouette forms on its way to the samples: ``(sums, counts)`` with ``sums[m, i, c]`` (``[M, n, k]``
+    float64, k the largest of ``n_clusters``) the sum over the rows j of cluster c under labeling m of the Euclidean
+    distance from row i to row j, and ``counts[m, c]`` (``[M, k]`` int32) the cluster sizes.  Arguments and limits as
+    for :func:`silhouette_samples`; ``labels`` of shape ``[n]`` count as one labeling (M = 1).  The pooled
+    within-cluster sum of the gap statistic is made of ``sums[m, i, labels[m, i]]``."""
+    return _silhouette_call(x, labels, n_clusters)[3:]
 
 
 def silhouette_samples(x: torch.Tensor, labels: torch.Tensor, n_clusters) -> torch.Tensor:

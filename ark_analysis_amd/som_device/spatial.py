@@ -1,5 +1,5 @@
 """Cell geometry: the neighbourhood matrix (K13), close-pair counts (K20), nearest-type distances (K14), nearest
-points (K23)."""
+points (K23), neighbourhood feature sums (K24)."""
 import operator
 from typing import Optional, Tuple
 
@@ -205,3 +205,48 @@ def nearest_indices(xy: torch.Tensor, seg: torch.Tensor, k: int, out: Optional[t
     xy = xy.contiguous()
     _capi.call("pxsom_nearest_indices", xy.data_ptr(), seg.data_ptr(), n_fovs, n, k, out.data_ptr(), _capi.stream_ptr())
     return out
+
+
+# ---- spatial-LDA neighbourhood sums (K24) ---------------------------------------------------------------------------
+def radius_threshold(radius, closed: bool = False) -> float:
+    """The double ``s_lim`` for pxsom_neighborhood_sums: for a squared distance s, ``s < s_lim`` holds exactly when
+    ``np.sqrt(s) < np.float64(radius)`` (``closed``: ``<=``).  sqrt is correctly rounded and monotone, so the test flips
+    at one double, found by bisection over the bit patterns as in :func:`neighbor_thresholds`.  This is not a test
+    against ``radius ** 2``: for a radius that is a power of two, sqrt of the double above ``radius ** 2`` rounds down
+    to ``radius``, so ``sqrt(s) <= radius`` holds where ``s <= radius ** 2`` does not.  A NaN radius is below nothing:
+    0.0."""
+    lim = np.float64(radius)
+    if np.isnan(lim):
+        return 0.0
+    with np.errstate(invalid="ignore"):
+        at = _smallest_double((lambda s: np.sqrt(s) > lim) if closed else (lambda s: np.sqrt(s) >= lim))
+    # no double's root is beyond the radius: every finite s is inside
+    return float("inf") if at is None else float(np.array(at, dtype=np.uint64).view(np.float64)[()])
+
+
+def neighborhood_sums(xy: torch.Tensor, feats: Optional[torch.Tensor], seg: torch.Tensor, radius,
+                      closed: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pxsom_neighborhood_sums: ``(sums [n, p] float64, counts [n] int32)`` on the device.  ``counts[i]`` is the number
+    of cells j of cell i's FOV, i included, with ``sqrt(fl(fl(dx * dx) + fl(dy * dy))) < radius`` in binary64
+    (``closed``: ``<=``) and ``sums[i]`` the sum of the rows ``feats[j]`` (``[n, p]`` float64) over them in ascending row
+    order, one add per row.  A row is taken by a select: a NaN or infinite feature reaches exactly the cells within the
+    radius of its cell.  ``feats=None``: only the counts, ``sums`` is ``[n, 0]``.  ``xy`` [n, 2] float64 (a cell with NaN
+    coordinates has count 0 and is nobody's neighbour), ``seg`` [F + 1] int64 offsets as for :func:`neighbor_counts`;
+    the rows need no order inside a FOV."""
+    def check_feats(n, dev):
+        if feats is not None and (feats.dim() != 2 or feats.shape[0] != n or feats.dtype != torch.float64
+                                  or feats.device != dev):
+            raise ValueError("feats must be an [n, p] float64 HBM tensor on xy's device, or None")
+    n, dev, seg, n_fovs = _cell_args(xy, seg, check_feats)
+    _check_offsets(seg, n)
+    p = 0 if feats is None else feats.shape[1]
+    s_lim = radius_threshold(radius, closed)
+    sums = torch.empty((n, p), dtype=torch.float64, device=dev)
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return sums, counts
+    xy = xy.contiguous()
+    feats = feats.contiguous() if p else None
+    _capi.call("pxsom_neighborhood_sums", xy.data_ptr(), feats.data_ptr() if p else None, seg.data_ptr(), n_fovs, n, p,
+               s_lim, sums.data_ptr() if p else None, counts.data_ptr(), _capi.stream_ptr())
+    return sums, counts

@@ -996,6 +996,29 @@ int pxsom_region_euler(const void *seg_dev, int seg_dtype, int64_t ld, int h, in
 int pxsom_nearest_indices(const double *xy_dev, const int64_t *seg_dev, int64_t n_fovs, int64_t n, int k,
                           int32_t *idx_dev, void *stream);
 
+/* ---- spatial-LDA featurisation: per cell, sums of feature rows over the cells within a radius (K24) -------------------
+ * reference: ark/spLDA/processing.py featurize_cell_table over spatial_lda's featurize_samples (behaviour as DESIGN.md K24
+ * states it; parity with spatial_lda itself unpinned).  Symbol added under ABI 9, none changed.  One stream-ordered launch
+ * covers the cohort.
+ *   xy_dev     [n, 2] binary64 centroids, 16-byte aligned; any order inside a FOV
+ *   feat_dev   [n, n_feat] binary64, row-major; may be null when n_feat == 0
+ *   seg_dev    [n_fovs + 1] int64 offsets, as for pxsom_neighbor_counts (clamped to [0, n] on the device)
+ *   n_feat     >= 0 (at most 8 * 65535); 0: only the counts are produced and sums_dev may be null
+ *   s_lim      cell j of the FOV of cell i (j = i included) is in i's neighbourhood when
+ *              s = fl(fl(dx * dx) + fl(dy * dy)) < s_lim, binary64 without contraction (som_device.radius_threshold
+ *              gives the s_lim for which this is sqrt(s) < radius, or <= radius, exactly)
+ *   counts_dev [n] int32, every entry written: the size of the neighbourhood; 0 for a row no FOV holds or with NaN
+ *              coordinates
+ *   sums_dev   [n, n_feat] binary64, every entry written: the sum of feat[j, t] over the neighbourhood in ascending row
+ *              order, one plain add per member starting from +0.0.  A member is taken by a select, not a product: a NaN
+ *              or infinite feature reaches exactly the cells within the radius of its cell.
+ * Every row is a query and every row of its FOV a candidate.  No atomics and no workspace: each output word is written
+ * once by its owner, the same input gives the same bits, the caller need not clear anything.  Offsets are clamped, so
+ * bad device-side input gives wrong rows, never an access outside the arrays.  Bad sizes, a NaN s_lim or null /
+ * misaligned pointers: PXSOM_ERR_INVALID_ARG before any HIP call; n == 0 returns PXSOM_OK without a launch. */
+int pxsom_neighborhood_sums(const double *xy_dev, const double *feat_dev, const int64_t *seg_dev, int64_t n_fovs,
+                            int64_t n, int n_feat, double s_lim, double *sums_dev, int32_t *counts_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
