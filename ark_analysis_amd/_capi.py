@@ -155,6 +155,14 @@ SYMBOLS = {
                                   _i32, _vp]),
     "pxsom_nearest_indices": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "pxsom_neighborhood_sums": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _f64, _vp, _vp, _vp]),
+    "pxsom_distance_transform_edt_workspace_bytes": (_sz, [_i32, _i32]),
+    "pxsom_distance_transform_edt": (_i32, [_vp, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "pxsom_plane_greater": (_i32, [_vp, _i32, _i32, _i64, _f64, _vp, _i64, _vp]),
+    "pxsom_plane_minmax_workspace_bytes": (_sz, []),
+    "pxsom_plane_minmax": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _sz, _vp]),
+    "pxsom_plane_histogram": (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp]),
+    "pxsom_sobel_magnitude": (_i32, [_vp, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "pxsom_class_markers": (_i32, [_vp, _i32, _i32, _i64, _f64, _f64, _vp, _i64, _vp]),
 }
 
 _lib = None

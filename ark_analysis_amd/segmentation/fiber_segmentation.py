@@ -14,11 +14,21 @@ The float columns come from ``regionprops_extraction.morphology`` on the host; s
 algorithms (``orientation`` as skimage 0.19 states it) and parity with skimage itself is not pinned.  The summaries
 are pandas on the host, as in the reference.
 
-Not built: the front half of ``segment_fibers`` -- ``equalize_adapthist``, ``frangi``, ``threshold_multiotsu``, ``sobel``
-and ``watershed``.  :func:`segment_fibers`, :func:`run_fiber_segmentation` and :func:`plot_fiber_segmentation_steps` keep
+Also built: the middle of ``segment_fibers``, from the ridge map (frangi's output) to the two planes the
+watershed receives -- :func:`fiber_watershed_inputs`: ``ridges > ridge_cutoff``, ``distance_transform_edt``, the sigma-1
+blur, the 256-bin histogram, ``threshold_multiotsu`` on its counts (:func:`threshold_multiotsu_from_histogram`, on the
+host), the 0 / 1 / 2 markers, the second blur and ``sobel``.  On the device: pxsom_plane_greater,
+pxsom_distance_transform_edt, pxsom_gaussian_blur_plane_mode, pxsom_plane_minmax, pxsom_plane_histogram,
+pxsom_class_markers, pxsom_sobel_magnitude.  The distance transform, the blurs, the histogram and the Sobel magnitude are
+scipy's / numpy's bits; the multi-Otsu choice on the counts is skimage 0.19's as recalled (``RECALLED_MULTIOTSU``), and
+skimage's ``sobel`` sums its 3 x 3 kernel in another order than scipy's separable one: parity with skimage is not pinned.
+
+Not built: ``equalize_adapthist`` and ``frangi`` before that middle, and ``watershed`` after it.
+:func:`segment_fibers`, :func:`run_fiber_segmentation` and :func:`plot_fiber_segmentation_steps` keep
 the reference's signatures, validate their paths and the channel as the reference does, and then raise
 NotImplementedError."""
 import os
+from collections import namedtuple
 from typing import Dict, Optional
 
 import numpy as np
@@ -69,6 +79,110 @@ def _label_and_filter_device(mask: np.ndarray, min_size: int) -> np.ndarray:
     fg = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).view(np.uint8)).to(_capi.require_gpu())
     labels, _, areas = som_device.label_components(fg, connectivity=1)
     return som_device.components_select(labels, areas, "keep", min_area=min_size, out=labels).cpu().numpy()
+
+
+def _watershed_inputs_device(ridges: np.ndarray, ridge_cutoff: float, sobel_blur: float, thresholds):
+    """som_device.watershed_inputs on a host ``[H, W]`` float64 plane: host arrays ``(dist, (t0, t1), markers, elevation)``;
+    ``thresholds(counts, edges)`` is the host's choice of the two thresholds."""
+    import torch
+    from .. import _capi, som_device
+    plane = torch.from_numpy(np.array(ridges, dtype=np.float64, order="C")).to(_capi.require_gpu())
+    dist, t, markers, elevation = som_device.watershed_inputs(plane, ridge_cutoff, sobel_blur, thresholds)
+    return dist.cpu().numpy(), t, markers.cpu().numpy(), elevation.cpu().numpy()
+
+
+# ---- from the ridge map to the watershed's inputs (K25) -------------------------------------------------------------------
+# Every detail of skimage 0.19's threshold_multiotsu that is recalled, not pinned by an installed skimage, as a named
+# switch; the first value of each is the default.
+#   prob        "float64": prob = counts / counts.sum() and all sums in binary64; "float32": cast as skimage casts, the
+#               sums in float32
+#   tie         "first" / "last": which pair (i, j), in row-major order, is taken among those that share the maximal
+#               criterion.  Ties are normal: moving a threshold across an empty bin leaves the criterion bit-equal.
+#   exact_bins  "occupied": with exactly `classes` occupied bins the thresholds are the first classes - 1 occupied bins;
+#               "search": the general search runs there too
+#   few_bins    "raise": ValueError with fewer than `classes` occupied bins; "search": the general search runs
+RECALLED_MULTIOTSU = {"prob": "float64", "tie": "first", "exact_bins": "occupied", "few_bins": "raise"}
+MULTIOTSU_CHOICES = {"prob": ("float64", "float32"), "tie": ("first", "last"), "exact_bins": ("occupied", "search"),
+                     "few_bins": ("raise", "search")}
+MULTIOTSU_FEW_VALUES = ("The input image has only %d different values. It cannot be thresholded in %d classes.")
+
+
+def threshold_multiotsu_from_histogram(counts, edges, classes=3, recalled=None):
+    """skimage 0.19's ``threshold_multiotsu(image, classes=3)`` from the ``nbins`` counts and ``nbins + 1`` edges of
+    ``np.histogram(image, nbins)``: ``prob = counts / counts.sum()``, zeroth and first moments over the bin index, and
+    over all ``i < j`` the pair that maximises ``sum S^2 / P`` over the classes ``[0 .. i]``, ``[i + 1 .. j]``,
+    ``[j + 1 .. nbins - 1]`` (a class with ``P = 0`` adds 0); the thresholds are the bin centres ``(e[k] + e[k + 1]) / 2``
+    at ``i`` and ``j``.  ``recalled``: overrides of ``RECALLED_MULTIOTSU``.  Only ``classes=3`` is built."""
+    if classes != 3:
+        raise NotImplementedError("threshold_multiotsu_from_histogram: classes=%r; only 3 classes are implemented" % (classes,))
+    rules = dict(RECALLED_MULTIOTSU, **(recalled or {}))
+    for name, value in rules.items():
+        if value not in MULTIOTSU_CHOICES.get(name, ()):
+            raise ValueError("RECALLED_MULTIOTSU: %s=%r is not one of %s" % (name, value, MULTIOTSU_CHOICES.get(name)))
+    counts = np.asarray(counts)
+    edges = np.asarray(edges, dtype=np.float64)
+    if counts.ndim != 1 or counts.size < classes or edges.shape != (counts.size + 1,):
+        raise ValueError("counts must be a vector of at least %d bins and edges one longer" % classes)
+    if counts.sum() <= 0 or (counts < 0).any():
+        raise ValueError("counts must be non-negative with a positive sum")
+    nbins = counts.size
+    centres = (edges[:-1] + edges[1:]) / 2
+    real = np.float32 if rules["prob"] == "float32" else np.float64
+    prob = (counts / counts.sum()).astype(real)
+    occupied = np.flatnonzero(prob > 0)
+    if occupied.size < classes and rules["few_bins"] == "raise":
+        raise ValueError(MULTIOTSU_FEW_VALUES % (occupied.size, classes))
+    if occupied.size == classes and rules["exact_bins"] == "occupied":
+        return centres[occupied[:-1]]
+    p = np.cumsum(prob, dtype=real)                                        # P[0 .. k]
+    s = np.cumsum(np.arange(nbins, dtype=real) * prob, dtype=real)         # S[0 .. k]
+
+    def term(pc, sc):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(pc > 0, sc * sc / pc, real(0))
+
+    i, j = np.triu_indices(nbins - 1, k=1)                                 # i < j <= nbins - 2, row-major
+    criterion = term(p[i], s[i]) + term(p[j] - p[i], s[j] - s[i]) + term(p[-1] - p[j], s[-1] - s[j])
+    best = np.flatnonzero(criterion == criterion.max())
+    k = best[0] if rules["tie"] == "first" else best[-1]
+    return centres[[i[k], j[k]]]
+
+
+WatershedInputs = namedtuple("WatershedInputs", ["distance_transformed", "thresholds", "markers", "elevation_map"])
+
+
+def fiber_watershed_inputs(ridges, ridge_cutoff=0.1, sobel_blur=1, out_dir=None, fov=None, debug=False):
+    """The middle of ``segment_fibers``: from ``ridges`` (``frangi(...) * 10000``, a ``[H, W]`` plane, taken as float64)
+    to what ``watershed`` receives.  Returns the host arrays ``(distance_transformed, thresholds, markers,
+    elevation_map)``: ``gaussian_filter(distance_transform_edt(ridges > ridge_cutoff), sigma=1)`` (float64),
+    ``threshold_multiotsu`` of it (float64 ``[2]``), the reference's ``threshed`` as int32 (0; 1 below the first
+    threshold; 2 above the second) and ``sobel(gaussian_filter(distance_transformed, sobel_blur))`` as int32.
+    With ``debug`` and ``out_dir`` (and ``fov``) the reference's two debug files of these stages are written:
+    ``_debug/<fov>_thresholded.tiff`` (the markers) and ``_debug/<fov>_ridges_thresholded.tiff`` (the distance map), both
+    as float32 -- the reference saves float64 planes, which image_io.write_image does not write; the markers are exact
+    in float32, the distance map is rounded once.
+    ValueError: a plane in which every pixel exceeds the cutoff (no background: no distance), and a distance map with
+    fewer than three occupied histogram bins (a plane without foreground among them); NotImplementedError: a
+    ``sobel_blur`` beyond the device blur's radius."""
+    from ..som_device.planes import check_blur_sigma
+    ridges = np.asarray(ridges)
+    if ridges.ndim != 2 or ridges.size == 0:
+        raise ValueError("ridges must be a non-empty [H, W] array, got shape %s" % (ridges.shape,))
+    check_blur_sigma(sobel_blur)
+    if debug and out_dir is not None:
+        validate_paths(out_dir)
+        if fov is None:
+            raise ValueError("debug files need fov")
+    dist, t, markers, elevation = _watershed_inputs_device(ridges.astype(np.float64), float(ridge_cutoff), sobel_blur,
+                                                           threshold_multiotsu_from_histogram)
+    got = WatershedInputs(np.asarray(dist, dtype=np.float64), np.asarray(t, dtype=np.float64),
+                          np.asarray(markers, dtype=np.int32), np.asarray(elevation, dtype=np.int32))
+    if debug and out_dir is not None:
+        folder = os.path.join(out_dir, "_debug")
+        os.makedirs(folder, exist_ok=True)
+        image_io.write_image(os.path.join(folder, f"{fov}_thresholded.tiff"), got.markers.astype(np.float32))
+        image_io.write_image(os.path.join(folder, f"{fov}_ridges_thresholded.tiff"), got.distance_transformed.astype(np.float32))
+    return got
 
 
 # ---- the object table -------------------------------------------------------------------------------------------------

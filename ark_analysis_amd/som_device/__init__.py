@@ -25,6 +25,8 @@ from .planes import (BIN_LEVEL, BIN_LOCAL, BIN_POSITIVE, BLUR_MAX_RADIUS, BLUR_M
                      choose_merges, cluster_mask, components_select, gaussian_blur_plane, gaussian_blur_plane_mode,
                      label_components, label_regions, merge_apply, merge_masks, object_mask, pair_overlaps, ridge_sign,
                      segmask_table, segmentation_mask, zero_by_segmentation, _blur_plane, _region_tables)
+from .planes import (EDT_NO_BACKGROUND, HISTOGRAM_MAX_BINS, class_markers, distance_transform_edt, histogram_edges,
+                     plane_greater, plane_histogram, plane_minmax, sobel_magnitude, watershed_inputs)
 from .cells import (CELLQUANT_FORCE_SEARCH, CELLQUANT_IMAGE_DTYPES, CELLQUANT_MODES, CELLQUANT_NUC_CAPACITY,
                     CONCAVITY_DEFAULTS, NUCSPLIT_FORCE_SEARCH, REGION_FORCE_SEARCH, REGION_MAX_SIDE, cell_quantify,
                     choose_splits, label_keys, nuclear_overlaps, region_euler, region_moments, region_props,

@@ -1,4 +1,6 @@
-"""Image planes and masks: cluster and segmentation masks, the plane blurs, object masks (K16, K22), mask merging (K18)."""
+"""Image planes and masks: cluster and segmentation masks, the plane blurs, object masks (K16, K22), mask merging (K18),
+the distance map, histogram, markers and elevation of fibre segmentation (K25)."""
+import operator
 from typing import Optional
 
 import numpy as np
@@ -475,3 +477,150 @@ def merge_masks(object_mask: torch.Tensor, cell_mask: torch.Tensor, overlap_thre
     winner, removed = choose_merges(pairs, object_bbox, cell_count, cell_sums, overlap_thresh, expansion_factor)
     dev = objects.device
     return merge_apply(objects, cells, torch.from_numpy(winner).to(dev), torch.from_numpy(removed).to(dev))
+
+
+# ---- fibre segmentation: distance map, histogram, markers, elevation (K25) ---------------------------------------------
+HISTOGRAM_MAX_BINS = 1024                            # kMaxBins of csrc/pxsom_markers.hip
+EDT_NO_BACKGROUND = "the plane has no background pixel: the distance transform is undefined"
+
+
+def _f64_plane(plane: torch.Tensor, what: str):
+    """``(h, w, ld)`` of a non-empty ``[H, W]`` float64 HBM plane with contiguous rows (any row stride)."""
+    if plane.dim() != 2 or not plane.is_cuda or plane.dtype != torch.float64:
+        raise ValueError("%s must be a 2-D float64 HBM tensor" % what)
+    h, w = plane.shape
+    if h == 0 or w == 0:
+        raise ValueError("%s must not be empty" % what)
+    if w > 1 and plane.stride(1) != 1:
+        raise ValueError("%s rows must be contiguous (stride(1) == 1)" % what)
+    return h, w, _ld(plane)
+
+
+def plane_greater(plane: torch.Tensor, level: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``plane > level`` of a ``[H, W]`` float64 HBM plane as uint8 1 / 0 (pxsom_plane_greater); a NaN pixel is 0."""
+    h, w, ld = _f64_plane(plane, "plane")
+    if np.isnan(float(level)):
+        raise ValueError("level must not be NaN")
+    out = _rows_plane(out, h, w, torch.uint8, plane.device, "out")
+    _capi.call("pxsom_plane_greater", plane.data_ptr(), h, w, ld, float(level), out.data_ptr(), _ld(out), _capi.stream_ptr())
+    return out
+
+
+def distance_transform_edt(fg: torch.Tensor, out: Optional[torch.Tensor] = None, squared: bool = False,
+                           check: bool = True) -> torch.Tensor:
+    """``scipy.ndimage.distance_transform_edt(fg)`` of a ``[H, W]`` uint8 / bool HBM plane (rows contiguous, any row
+    stride), scipy's bits: float64 ``[H, W]`` in HBM, or with ``squared`` the exact int32 squared distances (``out`` if
+    given: that dtype, rows contiguous, any row stride).  ``H^2 + W^2`` must fit an int32 (NotImplementedError).  A plane
+    without a background pixel has no answer: pxsom_distance_transform_edt writes +inf (squared: 2^31 - 1) everywhere, and
+    this function reads one pixel back and raises ValueError; ``check=False`` leaves that to the caller and does not
+    synchronise."""
+    fg = _binary_plane(fg, "fg")
+    h, w = fg.shape
+    if h * h + w * w > 2 ** 31 - 1:
+        raise NotImplementedError("distance_transform_edt: H^2 + W^2 of a %d x %d plane is beyond int32" % (h, w))
+    out = _rows_plane(out, h, w, torch.int32 if squared else torch.float64, fg.device, "out")
+    wsb = _capi.lib().pxsom_distance_transform_edt_workspace_bytes(h, w)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=fg.device)
+    _capi.call("pxsom_distance_transform_edt", fg.data_ptr(), h, w, _ld(fg), None if squared else out.data_ptr(), _ld(out),
+               out.data_ptr() if squared else None, _ld(out), ws.data_ptr(), wsb, _capi.stream_ptr())
+    if check and out[0, 0].item() == (2 ** 31 - 1 if squared else float("inf")):
+        raise ValueError(EDT_NO_BACKGROUND)
+    return out
+
+
+def plane_minmax(plane: torch.Tensor):
+    """``(plane.min(), plane.max())`` of a ``[H, W]`` float64 HBM plane as two Python floats (pxsom_plane_minmax; the two
+    doubles are read back).  ValueError for a plane that holds a NaN."""
+    h, w, ld = _f64_plane(plane, "plane")
+    both = torch.empty(2, dtype=torch.float64, device=plane.device)
+    wsb = _capi.lib().pxsom_plane_minmax_workspace_bytes()
+    ws = torch.empty(wsb, dtype=torch.uint8, device=plane.device)
+    _capi.call("pxsom_plane_minmax", plane.data_ptr(), h, w, ld, both.data_ptr(), ws.data_ptr(), wsb, _capi.stream_ptr())
+    lo, hi = both.tolist()
+    if np.isnan(lo):
+        raise ValueError("the plane holds a NaN")
+    return lo, hi
+
+
+def histogram_edges(lo: float, hi: float, nbins: int) -> np.ndarray:
+    """The ``nbins + 1`` edges np.histogram makes for the range ``(lo, hi)``: ``lo == hi`` widens by 0.5 on each side."""
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError("autodetected range of [%s, %s] is not finite" % (lo, hi))
+    if lo == hi:
+        lo, hi = lo - 0.5, hi + 0.5
+    return np.linspace(lo, hi, nbins + 1, endpoint=True, dtype=np.float64)
+
+
+def plane_histogram(plane: torch.Tensor, nbins: int = 256, value_range=None):
+    """``np.histogram(plane, nbins)`` of a ``[H, W]`` float64 HBM plane -> ``(counts, edges)``: int64 ``[nbins]`` in HBM
+    and the float64 edges on the host.  The range is the plane's own minimum and maximum (:func:`plane_minmax`, or
+    ``value_range`` when the caller has them); numpy makes the edges from it on the host and pxsom_plane_histogram counts
+    against them, so the counts are numpy's whatever the rounding of a bin estimate.  ValueError for NaN or an infinite
+    range, as numpy raises."""
+    h, w, ld = _f64_plane(plane, "plane")
+    nbins = operator.index(nbins)
+    if not 1 <= nbins <= HISTOGRAM_MAX_BINS:
+        raise ValueError("nbins must lie in 1 .. %d, got %d" % (HISTOGRAM_MAX_BINS, nbins))
+    lo, hi = plane_minmax(plane) if value_range is None else (float(value_range[0]), float(value_range[1]))
+    edges = histogram_edges(lo, hi, nbins)
+    counts = torch.empty(nbins, dtype=torch.int64, device=plane.device)
+    _capi.call("pxsom_plane_histogram", plane.data_ptr(), h, w, ld, torch.from_numpy(edges).to(plane.device).data_ptr(), nbins,
+               counts.data_ptr(), _capi.stream_ptr())
+    return counts, edges
+
+
+def sobel_magnitude(plane: torch.Tensor, out: Optional[torch.Tensor] = None, as_int32: bool = False) -> torch.Tensor:
+    """``sqrt((a * a + b * b) / 2)`` with ``a, b = scipy.ndimage.sobel(plane, axis, mode='reflect') / 4`` of a ``[H, W]``
+    float64 HBM plane, scipy's bits (pxsom_sobel_magnitude; skimage.filters.sobel sums the same 3 x 3 kernel in another
+    order).  float64, or with ``as_int32`` the magnitude converted toward zero (``out`` if given: that dtype, rows
+    contiguous, any row stride, not the plane)."""
+    h, w, ld = _f64_plane(plane, "plane")
+    out = _rows_plane(out, h, w, torch.int32 if as_int32 else torch.float64, plane.device, "out")
+    _capi.call("pxsom_sobel_magnitude", plane.data_ptr(), h, w, ld, None if as_int32 else out.data_ptr(), _ld(out),
+               out.data_ptr() if as_int32 else None, _ld(out), _capi.stream_ptr())
+    return out
+
+
+def class_markers(dist: torch.Tensor, t0: float, t1: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 ``[H, W]`` markers of a float64 HBM plane: 0, then 1 where ``dist < t0``, then 2 where ``dist > t1``
+    (pxsom_class_markers)."""
+    h, w, ld = _f64_plane(dist, "dist")
+    if np.isnan(float(t0)) or np.isnan(float(t1)):
+        raise ValueError("thresholds must not be NaN")
+    out = _label_plane(out, h, w, dist.device, "out")
+    _capi.call("pxsom_class_markers", dist.data_ptr(), h, w, ld, float(t0), float(t1), out.data_ptr(), _ld(out), _capi.stream_ptr())
+    return out
+
+
+def watershed_inputs(ridges: torch.Tensor, ridge_cutoff: float, sobel_blur: float, thresholds=None,
+                     markers: Optional[torch.Tensor] = None, elevation: Optional[torch.Tensor] = None):
+    """The device chain of ``segment_fibers`` between frangi and watershed on a contiguous ``[H, W]`` float64 HBM plane:
+
+      fg        ``ridges > ridge_cutoff``                                   :func:`plane_greater`
+      dist      ``gaussian_filter(distance_transform_edt(fg), 1)``           :func:`distance_transform_edt`, the plane blur
+      counts    ``np.histogram(dist, 256)``                                  :func:`plane_minmax`, :func:`plane_histogram`
+      t0, t1    ``thresholds(counts, edges)`` on the host (default: fiber_segmentation.threshold_multiotsu_from_histogram)
+      markers   0 / 1 (``dist < t0``) / 2 (``dist > t1``), int32              :func:`class_markers`
+      elevation ``sobel(gaussian_filter(dist, sobel_blur))`` as int32        the plane blur, :func:`sobel_magnitude`
+
+    Returns ``(dist, (t0, t1), markers, elevation)``, the planes in HBM (``markers`` / ``elevation`` if given: int32, rows
+    contiguous, any row stride).  The host sees the minimum and maximum (two doubles down, 257 edges up) and the 256
+    counts; the thresholds return as kernel arguments.  ValueError for a plane without background (the distance map is
+    +inf) and whatever ``thresholds`` raises."""
+    if ridges.dim() != 2 or not ridges.is_cuda or ridges.dtype != torch.float64 or not ridges.is_contiguous() or not ridges.numel():
+        raise ValueError("ridges must be a non-empty contiguous 2-D float64 HBM tensor")
+    check_blur_sigma(sobel_blur)
+    if thresholds is None:
+        from ..segmentation.fiber_segmentation import threshold_multiotsu_from_histogram as thresholds
+    fg = plane_greater(ridges, ridge_cutoff)
+    edt = distance_transform_edt(fg, check=False)
+    dist = gaussian_blur_plane_mode(edt, 1, "reflect")
+    lo, hi = plane_minmax(dist)
+    if hi == float("inf"):
+        raise ValueError(EDT_NO_BACKGROUND)
+    counts, edges = plane_histogram(dist, 256, (lo, hi))
+    t0, t1 = (float(t) for t in thresholds(counts.cpu().numpy(), edges))
+    markers = class_markers(dist, t0, t1, out=markers)
+    smooth = gaussian_blur_plane_mode(dist, sobel_blur, "reflect", out=edt)
+    elevation = sobel_magnitude(smooth, out=elevation, as_int32=True)
+    return dist, (t0, t1), markers, elevation

@@ -1019,6 +1019,62 @@ int pxsom_nearest_indices(const double *xy_dev, const int64_t *seg_dev, int64_t 
 int pxsom_neighborhood_sums(const double *xy_dev, const double *feat_dev, const int64_t *seg_dev, int64_t n_fovs,
                             int64_t n, int n_feat, double s_lim, double *sums_dev, int32_t *counts_dev, void *stream);
 
+/* ---- fibre segmentation, from the ridge map to the inputs of the watershed (K25) --------------------------------------
+ * reference: ark/segmentation/fiber_segmentation.py segment_fibers, between frangi and watershed:
+ *   fg = ridges > ridge_cutoff;  dist = gaussian_filter(distance_transform_edt(fg), 1)
+ *   t0, t1 = threshold_multiotsu(dist, 3) (the 256-bin histogram here, the choice on the host)
+ *   markers = 0, 1 where dist < t0, 2 where dist > t1;  elevation = sobel(gaussian_filter(dist, sobel_blur)) as int32
+ * (the two blurs are pxsom_gaussian_blur_plane_mode).  Symbols added under ABI 9, none changed.  Planes are [h, w] with
+ * contiguous rows and a row stride in elements; h * w <= 2^31 - 1 (PXSOM_ERR_UNSUPPORTED beyond).  Null or misaligned
+ * pointers, sizes < 1, strides < w, NaN scalars: PXSOM_ERR_INVALID_ARG before any HIP call; a short or null workspace:
+ * PXSOM_ERR_WORKSPACE.  Integer atomics or none: the same input gives the same bits on every run.
+ *
+ * pxsom_distance_transform_edt: scipy.ndimage.distance_transform_edt(fg != 0).
+ *   fg_dev   [h, w] uint8, row stride ld; 0 is background
+ *   sq_dev   [h, w] int32, row stride ldsq, or NULL: the exact squared distance to the nearest background pixel (0 on the
+ *            background)
+ *   out_dev  [h, w] binary64, row stride ldo, or NULL: sqrt((double)sq), correctly rounded -- scipy's bits.  One of
+ *            the two outputs must be given.
+ *   A plane WITHOUT a background pixel has no nearest one: sq = INT32_MAX and out = +inf at every pixel (scipy measures
+ *   to a point outside the image there).  h * h + w * w <= INT32_MAX, PXSOM_ERR_UNSUPPORTED beyond: every intermediate
+ *   is then an int32.  Workspace: pxsom_distance_transform_edt_workspace_bytes(h, w) (the int32 column distances and a
+ *   summary per band of 256 rows; 0 for refused sizes), 8-byte aligned.
+ *
+ * pxsom_plane_greater: out_dev [h, w] uint8 (row stride ldo) = plane > level, 1 / 0; a NaN pixel is 0.
+ *
+ * pxsom_plane_minmax: minmax_dev[0] = the smallest, minmax_dev[1] = the largest value of the plane; both NaN when the
+ * plane holds a NaN.  Workspace: pxsom_plane_minmax_workspace_bytes().
+ *
+ * pxsom_plane_histogram: counts_dev [nbins] int64 (cleared here), nbins in 1 .. 1024, over edges_dev [nbins + 1]
+ * ascending binary64 edges: bin i counts e[i] <= v < e[i + 1], the last bin also v == e[nbins]; a value outside
+ * [e[0], e[nbins]] or NaN is counted nowhere.  With the edges numpy makes -- np.linspace(lo, hi, nbins + 1) -- the counts
+ * are np.histogram(plane, nbins, (lo, hi))[0]: the kernel estimates a bin and then moves it until the edge test holds, so
+ * the rounding of the estimate never shows.
+ *
+ * pxsom_sobel_magnitude: m = sqrt((a * a + b * b) / 2) with a, b = scipy.ndimage.sobel(plane, axis = 0, 1,
+ * mode="reflect") / 4, binary64 without contraction in scipy's term order (difference [-1, 0, 1] along the axis, then
+ * [1, 2, 1] along the other) -- scipy's bits, for any size from 1 x 1; the reflected border is resolved per index.
+ *   out_dev     [h, w] binary64, row stride ldo, or NULL
+ *   out_i32_dev [h, w] int32, row stride ldi, or NULL: m converted toward zero (numpy's astype for finite m < 2^31)
+ *   One of the two must be given; neither may overlap the plane.
+ *
+ * pxsom_class_markers: out_dev [h, w] int32 (row stride ldo) = 0, then 1 where v < t0, then 2 where v > t1, compared in
+ * binary64; a NaN pixel is 0. */
+size_t pxsom_distance_transform_edt_workspace_bytes(int h, int w);
+int pxsom_distance_transform_edt(const uint8_t *fg_dev, int h, int w, int64_t ld, double *out_dev, int64_t ldo,
+                                 int32_t *sq_dev, int64_t ldsq, void *workspace_dev, size_t workspace_bytes, void *stream);
+int pxsom_plane_greater(const double *plane_dev, int h, int w, int64_t ld, double level, uint8_t *out_dev, int64_t ldo,
+                        void *stream);
+size_t pxsom_plane_minmax_workspace_bytes(void);
+int pxsom_plane_minmax(const double *plane_dev, int h, int w, int64_t ld, double *minmax_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream);
+int pxsom_plane_histogram(const double *plane_dev, int h, int w, int64_t ld, const double *edges_dev, int nbins,
+                          int64_t *counts_dev, void *stream);
+int pxsom_sobel_magnitude(const double *plane_dev, int h, int w, int64_t ld, double *out_dev, int64_t ldo,
+                          int32_t *out_i32_dev, int64_t ldi, void *stream);
+int pxsom_class_markers(const double *dist_dev, int h, int w, int64_t ld, double t0, double t1, int32_t *out_dev,
+                        int64_t ldo, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
