@@ -163,6 +163,7 @@ SYMBOLS = {
     "pxsom_plane_histogram": (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp]),
     "pxsom_sobel_magnitude": (_i32, [_vp, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
     "pxsom_class_markers": (_i32, [_vp, _i32, _i32, _i64, _f64, _f64, _vp, _i64, _vp]),
+    "pxsom_frangi_scale": (_i32, [_vp, _i64, _i32, _i32, _f64, _f64, _f64, _i32, _f64, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -23,7 +23,15 @@ pxsom_class_markers, pxsom_sobel_magnitude.  The distance transform, the blurs, 
 scipy's / numpy's bits; the multi-Otsu choice on the counts is skimage 0.19's as recalled (``RECALLED_MULTIOTSU``), and
 skimage's ``sobel`` sums its 3 x 3 kernel in another order than scipy's separable one: parity with skimage is not pinned.
 
-Not built: ``equalize_adapthist`` and ``frangi`` before that middle, and ``watershed`` after it.
+Also built: the ``frangi`` stage before that middle -- :func:`frangi_ridges`, the ridge map
+``frangi(contrast_adjusted, sigmas=fiber_widths, black_ridges=False) * 10000`` in skimage 0.19's 2-D statement as recalled
+(np.gradient twice on the reflect-mode blur, the eigenvalues ordered by magnitude, the maximum over the widths), and
+:func:`fiber_watershed_inputs_from_contrast`, which runs it and the K25 middle as one chain on the device.  On the device:
+pxsom_gaussian_blur_plane_mode and pxsom_frangi_scale, one of each per width.  The blur is scipy's bits; the rest equals
+the numpy statement of tests/frangi_reference.py bit for bit, including its own exponential; parity with skimage itself
+is not pinned.
+
+Not built: ``equalize_adapthist`` before ``frangi``, and ``watershed`` after the middle.
 :func:`segment_fibers`, :func:`run_fiber_segmentation` and :func:`plot_fiber_segmentation_steps` keep
 the reference's signatures, validate their paths and the channel as the reference does, and then raise
 NotImplementedError."""
@@ -89,6 +97,24 @@ def _watershed_inputs_device(ridges: np.ndarray, ridge_cutoff: float, sobel_blur
     plane = torch.from_numpy(np.array(ridges, dtype=np.float64, order="C")).to(_capi.require_gpu())
     dist, t, markers, elevation = som_device.watershed_inputs(plane, ridge_cutoff, sobel_blur, thresholds)
     return dist.cpu().numpy(), t, markers.cpu().numpy(), elevation.cpu().numpy()
+
+
+def _frangi_device(image: np.ndarray, sigmas, beta: float, gamma: float, scale: float) -> np.ndarray:
+    """som_device.frangi on a host ``[H, W]`` float64 plane: the host array ``frangi(image, sigmas, beta, gamma) * scale``."""
+    import torch
+    from .. import _capi, som_device
+    plane = torch.from_numpy(np.array(image, dtype=np.float64, order="C")).to(_capi.require_gpu())
+    return som_device.frangi(plane, sigmas, beta, gamma, scale).cpu().numpy()
+
+
+def _ridge_watershed_inputs_device(contrast: np.ndarray, sigmas, ridge_cutoff: float, sobel_blur: float, thresholds):
+    """som_device.ridge_watershed_inputs on a host ``[H, W]`` float64 plane, one upload and one chain on the device: host
+    arrays ``(ridges, dist, (t0, t1), markers, elevation)``."""
+    import torch
+    from .. import _capi, som_device
+    plane = torch.from_numpy(np.array(contrast, dtype=np.float64, order="C")).to(_capi.require_gpu())
+    ridges, dist, t, markers, elevation = som_device.ridge_watershed_inputs(plane, sigmas, ridge_cutoff, sobel_blur, thresholds)
+    return ridges.cpu().numpy(), dist.cpu().numpy(), t, markers.cpu().numpy(), elevation.cpu().numpy()
 
 
 # ---- from the ridge map to the watershed's inputs (K25) -------------------------------------------------------------------
@@ -169,20 +195,87 @@ def fiber_watershed_inputs(ridges, ridge_cutoff=0.1, sobel_blur=1, out_dir=None,
     if ridges.ndim != 2 or ridges.size == 0:
         raise ValueError("ridges must be a non-empty [H, W] array, got shape %s" % (ridges.shape,))
     check_blur_sigma(sobel_blur)
-    if debug and out_dir is not None:
-        validate_paths(out_dir)
-        if fov is None:
-            raise ValueError("debug files need fov")
+    _check_debug(out_dir, fov, debug)
     dist, t, markers, elevation = _watershed_inputs_device(ridges.astype(np.float64), float(ridge_cutoff), sobel_blur,
                                                            threshold_multiotsu_from_histogram)
     got = WatershedInputs(np.asarray(dist, dtype=np.float64), np.asarray(t, dtype=np.float64),
                           np.asarray(markers, dtype=np.int32), np.asarray(elevation, dtype=np.int32))
+    _write_debug(out_dir, fov, debug, thresholded=got.markers, ridges_thresholded=got.distance_transformed)
+    return got
+
+
+def _check_debug(out_dir, fov, debug):
+    """Debug files are written with ``debug`` and an ``out_dir``: that folder must exist and ``fov`` must name them."""
+    if debug and out_dir is not None:
+        validate_paths(out_dir)
+        if fov is None:
+            raise ValueError("debug files need fov")
+
+
+def _write_debug(out_dir, fov, debug, **planes):
+    """``_debug/<fov>_<name>.tiff`` per plane, as float32: the reference saves float64 planes, which
+    image_io.write_image does not write."""
     if debug and out_dir is not None:
         folder = os.path.join(out_dir, "_debug")
         os.makedirs(folder, exist_ok=True)
-        image_io.write_image(os.path.join(folder, f"{fov}_thresholded.tiff"), got.markers.astype(np.float32))
-        image_io.write_image(os.path.join(folder, f"{fov}_ridges_thresholded.tiff"), got.distance_transformed.astype(np.float32))
-    return got
+        for name, plane in planes.items():
+            image_io.write_image(os.path.join(folder, f"{fov}_{name}.tiff"), plane.astype(np.float32))
+
+
+# ---- the ridge map (K26) ---------------------------------------------------------------------------------------------------
+def _contrast_plane(image, what):
+    image = np.asarray(image)
+    if image.ndim != 2 or image.size == 0:
+        raise ValueError("%s must be a non-empty [H, W] array, got shape %s" % (what, image.shape))
+    if min(image.shape) < 2:
+        from ..som_device.planes import GRADIENT_TOO_SMALL
+        raise ValueError(GRADIENT_TOO_SMALL)
+    return image.astype(np.float64)
+
+
+def frangi_ridges(image, fiber_widths=range(1, 10, 2), beta=0.5, gamma=15, scale=10000, out_dir=None, fov=None, debug=False,
+                  black_ridges=False):
+    """The ``frangi`` stage of ``segment_fibers``: ``frangi(image, sigmas=fiber_widths, black_ridges=False) * scale`` of a
+    ``[H, W]`` plane (taken as float64; ``H, W >= 2``) as a float64 host array -- with the defaults the reference's
+    ``ridges``.  skimage 0.19's 2-D statement as recalled (``alpha`` only enters the 3-D formula); one
+    plane blur and one launch of pxsom_frangi_scale per width.  With ``debug`` and ``out_dir`` (and ``fov``) the
+    reference's debug file of this stage is written: ``_debug/<fov>_frangi_filter.tiff``, as float32 -- the reference
+    saves a float64 plane, which image_io.write_image does not write; the ridge map is rounded once.
+    ValueError: no width, a negative one ("Sigma values less than zero are not valid"), width 0 (skimage returns zeros
+    there), ``beta`` or ``gamma`` not finite or <= 0, a plane with a side of 1 (numpy's message); NotImplementedError: a
+    width beyond the device blur's radius, ``black_ridges=True``, ``gamma=None`` (skimage >= 0.20's default)."""
+    from ..som_device.planes import frangi_arguments
+    image = _contrast_plane(image, "image")
+    sigmas, _, _ = frangi_arguments(fiber_widths, beta, gamma, black_ridges)
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError("scale must be finite, got %r" % (scale,))
+    _check_debug(out_dir, fov, debug)
+    ridges = np.asarray(_frangi_device(image, sigmas, float(beta), float(gamma), scale), dtype=np.float64)
+    _write_debug(out_dir, fov, debug, frangi_filter=ridges)
+    return ridges
+
+
+def fiber_watershed_inputs_from_contrast(contrast_adjusted, fiber_widths=range(1, 10, 2), ridge_cutoff=0.1, sobel_blur=1,
+                                         out_dir=None, fov=None, debug=False):
+    """``segment_fibers`` from ``equalize_adapthist``'s result to what ``watershed`` receives, as one chain on the device:
+    :func:`frangi_ridges` (the reference's defaults, ``* 10000``) and :func:`fiber_watershed_inputs` without the ridge map
+    crossing to the host in between.  Returns ``(inputs, ridges)``: the ``WatershedInputs`` and the float64 ridge plane.
+    With ``debug`` and ``out_dir`` (and ``fov``) the three debug files of these stages are written
+    (``_debug/<fov>_frangi_filter.tiff``, ``_thresholded.tiff``, ``_ridges_thresholded.tiff``, float32).  Errors: those of
+    the two functions."""
+    from ..som_device.planes import check_blur_sigma, frangi_arguments
+    contrast = _contrast_plane(contrast_adjusted, "contrast_adjusted")
+    sigmas, _, _ = frangi_arguments(fiber_widths, 0.5, 15)
+    check_blur_sigma(sobel_blur)
+    _check_debug(out_dir, fov, debug)
+    ridges, dist, t, markers, elevation = _ridge_watershed_inputs_device(contrast, sigmas, float(ridge_cutoff), sobel_blur,
+                                                                         threshold_multiotsu_from_histogram)
+    got = WatershedInputs(np.asarray(dist, dtype=np.float64), np.asarray(t, dtype=np.float64),
+                          np.asarray(markers, dtype=np.int32), np.asarray(elevation, dtype=np.int32))
+    ridges = np.asarray(ridges, dtype=np.float64)
+    _write_debug(out_dir, fov, debug, frangi_filter=ridges, thresholded=got.markers, ridges_thresholded=got.distance_transformed)
+    return got, ridges
 
 
 # ---- the object table -------------------------------------------------------------------------------------------------

@@ -27,6 +27,7 @@ from .planes import (BIN_LEVEL, BIN_LOCAL, BIN_POSITIVE, BLUR_MAX_RADIUS, BLUR_M
                      segmask_table, segmentation_mask, zero_by_segmentation, _blur_plane, _region_tables)
 from .planes import (EDT_NO_BACKGROUND, HISTOGRAM_MAX_BINS, class_markers, distance_transform_edt, histogram_edges,
                      plane_greater, plane_histogram, plane_minmax, sobel_magnitude, watershed_inputs)
+from .planes import FRANGI_SIGMAS, GRADIENT_TOO_SMALL, frangi, frangi_arguments, ridge_watershed_inputs
 from .cells import (CELLQUANT_FORCE_SEARCH, CELLQUANT_IMAGE_DTYPES, CELLQUANT_MODES, CELLQUANT_NUC_CAPACITY,
                     CONCAVITY_DEFAULTS, NUCSPLIT_FORCE_SEARCH, REGION_FORCE_SEARCH, REGION_MAX_SIDE, cell_quantify,
                     choose_splits, label_keys, nuclear_overlaps, region_euler, region_moments, region_props,

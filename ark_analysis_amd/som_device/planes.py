@@ -1,5 +1,5 @@
 """Image planes and masks: cluster and segmentation masks, the plane blurs, object masks (K16, K22), mask merging (K18),
-the distance map, histogram, markers and elevation of fibre segmentation (K25)."""
+the distance map, histogram, markers and elevation of fibre segmentation (K25), its Frangi ridge filter (K26)."""
 import operator
 from typing import Optional
 
@@ -624,3 +624,83 @@ def watershed_inputs(ridges: torch.Tensor, ridge_cutoff: float, sobel_blur: floa
     smooth = gaussian_blur_plane_mode(dist, sobel_blur, "reflect", out=edt)
     elevation = sobel_magnitude(smooth, out=elevation, as_int32=True)
     return dist, (t0, t1), markers, elevation
+
+
+# ---- fibre segmentation: the Frangi ridge filter (K26) -------------------------------------------------------------------
+FRANGI_SIGMAS = (1, 3, 5, 7, 9)                      # the reference's fiber_widths, range(1, 10, 2)
+GRADIENT_TOO_SMALL = ("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements "
+                      "are required.")
+
+
+def frangi_arguments(sigmas, beta, gamma, black_ridges=False):
+    """The checked arguments of the Frangi filter, without a device: ``(sigmas, bsq, gsq)`` with ``sigmas`` a list of
+    Python floats (any iterable of numbers, flattened as skimage flattens it) and ``bsq = 2 beta^2``, ``gsq = 2 gamma^2``
+    in host doubles.  ValueError: no sigma, a negative one (skimage's text), sigma 0 (skimage returns zeros there: a
+    deliberate narrowing), a sigma, ``beta`` or ``gamma`` that is not finite, ``beta`` or ``gamma`` <= 0.
+    NotImplementedError: a sigma beyond the plane blur's radius, ``black_ridges=True``, ``gamma=None`` (skimage >= 0.20's
+    data-dependent default)."""
+    if black_ridges:
+        raise NotImplementedError("frangi: black_ridges=True is not implemented (the reference passes False)")
+    if gamma is None:
+        raise NotImplementedError("frangi: gamma=None (skimage >= 0.20's data-dependent default) is not implemented; "
+                                  "skimage 0.19's default is 15")
+    if not isinstance(sigmas, np.ndarray) and hasattr(sigmas, "__iter__"):
+        sigmas = list(sigmas)
+    flat = np.asarray(sigmas, dtype=np.float64).ravel()
+    if flat.size == 0:
+        raise ValueError("frangi needs at least one sigma")
+    if np.any(flat < 0.0):
+        raise ValueError("Sigma values less than zero are not valid")
+    if not np.all(np.isfinite(flat)):
+        raise ValueError("frangi takes finite sigmas, got %r" % (flat.tolist(),))
+    if np.any(flat == 0.0):
+        raise ValueError("frangi: sigma 0 is not taken (skimage returns zeros for it)")
+    for s in flat.tolist():
+        check_blur_sigma(s)
+    beta, gamma = float(beta), float(gamma)
+    if not (np.isfinite(beta) and beta > 0 and np.isfinite(gamma) and gamma > 0):
+        raise ValueError("frangi takes finite beta and gamma > 0, got %r and %r" % (beta, gamma))
+    return [float(s) for s in flat], 2.0 * beta * beta, 2.0 * gamma * gamma
+
+
+def _byte_range(t: torch.Tensor):
+    return t.data_ptr(), t.data_ptr() + ((t.shape[0] - 1) * _ld(t) + t.shape[1]) * t.element_size()
+
+
+def frangi(plane: torch.Tensor, sigmas=FRANGI_SIGMAS, beta=0.5, gamma=15.0, scale=1.0,
+           out: Optional[torch.Tensor] = None, black_ridges: bool = False) -> torch.Tensor:
+    """``skimage.filters.frangi(plane, sigmas, beta=beta, gamma=gamma, black_ridges=False, mode="reflect") * scale`` in
+    skimage 0.19's 2-D statement (include/pxsom.h "K26"; parity with skimage itself is unpinned) of a ``[H, W]`` float64
+    HBM plane (rows contiguous, any row stride; ``H, W >= 2``) -> float64 ``[H, W]`` in HBM (``out`` if given: rows
+    contiguous, any row stride, not sharing memory with the plane).  Per scale the reflect-mode plane blur runs into one
+    reused temporary and one launch of pxsom_frangi_scale folds that scale's vesselness into the result, the last one
+    applying ``scale``; no host synchronisation.  The arguments are those of :func:`frangi_arguments`."""
+    h, w, _ = _f64_plane(plane, "plane")
+    if h < 2 or w < 2:
+        raise ValueError(GRADIENT_TOO_SMALL)
+    sigmas, bsq, gsq = frangi_arguments(sigmas, beta, gamma, black_ridges)
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError("scale must be finite, got %r" % (scale,))
+    out = _rows_plane(out, h, w, torch.float64, plane.device, "out")
+    lo, hi = _byte_range(out)
+    plo, phi = _byte_range(plane)
+    if lo < phi and plo < hi:
+        raise ValueError("out must not share memory with the plane: every scale blurs the plane again")
+    x = plane.contiguous()                           # the blur takes contiguous planes
+    g, tmp = torch.empty_like(x), torch.empty_like(x)
+    for i, sigma in enumerate(sigmas):
+        gaussian_blur_plane_mode(x, sigma, "reflect", out=g, tmp=tmp)
+        _capi.call("pxsom_frangi_scale", g.data_ptr(), _ld(g), h, w, sigma ** 2, bsq, gsq, int(i == 0),
+                   scale if i == len(sigmas) - 1 else 1.0, out.data_ptr(), _ld(out), _capi.stream_ptr())
+    return out
+
+
+def ridge_watershed_inputs(contrast: torch.Tensor, sigmas=FRANGI_SIGMAS, ridge_cutoff: float = 0.1, sobel_blur: float = 1,
+                           thresholds=None, beta=0.5, gamma=15.0):
+    """The device chain of ``segment_fibers`` from the contrast-adjusted plane (``equalize_adapthist``'s result, a ``[H, W]``
+    float64 HBM plane) to what ``watershed`` receives: ``ridges = frangi(contrast, sigmas, beta, gamma) * 10000``
+    (:func:`frangi`), then :func:`watershed_inputs` on it.  Returns ``(ridges, dist, (t0, t1), markers, elevation)``; the
+    ridge map stays in HBM."""
+    ridges = frangi(contrast, sigmas, beta, gamma, scale=10000.0)
+    return (ridges,) + tuple(watershed_inputs(ridges, ridge_cutoff, sobel_blur, thresholds))

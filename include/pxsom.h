@@ -1075,6 +1075,33 @@ int pxsom_sobel_magnitude(const double *plane_dev, int h, int w, int64_t ld, dou
 int pxsom_class_markers(const double *dist_dev, int h, int w, int64_t ld, double t0, double t1, int32_t *out_dev,
                         int64_t ldo, void *stream);
 
+/* ---- fibre segmentation, the Frangi ridge filter (K26) -------------------------------------------------------------------
+ * reference: ark/segmentation/fiber_segmentation.py segment_fibers, `frangi(contrast_adjusted, sigmas=fiber_widths,
+ * black_ridges=False) * 10000`, in skimage 0.19's 2-D statement as recalled (parity with skimage itself is unpinned).
+ * Symbol added under ABI 9, none changed.
+ *
+ * pxsom_frangi_scale: one scale.  g_dev is gaussian_filter(x, sigma, mode="reflect") (pxsom_gaussian_blur_plane_mode),
+ * s2 = sigma^2, bsq = 2 beta^2, gsq = 2 gamma^2.  Per pixel, in binary64 without contraction:
+ *   g0, g1 = np.gradient(g, axis=0), np.gradient(g, axis=1)        ((f[i+1] - f[i-1]) / 2 inside, one-sided at both ends)
+ *   hrr, hrc, hcc = s2 * np.gradient(g0, axis=0), s2 * np.gradient(g0, axis=1), s2 * np.gradient(g1, axis=1)
+ *   d = hrr - hcc;  r = sqrt(d*d + 4*(hrc*hrc));  t = hrr + hcc;  e_hi, e_lo = (t + r) / 2, (t - r) / 2
+ *   big, small = the eigenvalue of larger and of smaller magnitude (|e_lo| >= |e_hi| takes e_lo as big: K22's rule)
+ *   den = |big|, 1e-10 where that is 0;  q = small / den;  rb = q*q;  rg = small*small + big*big
+ *   v = exp_neg(-rb / bsq) * (1 - exp_neg(-rg / gsq)),  0 where big > 0
+ *   out = np.maximum(first ? 0 : out, v) * scale                   (a NaN on either side stays)
+ * exp_neg(t), t <= 0, is the contract's own exponential in plain binary64 operations: 0 for t < -708, NaN for NaN, else
+ * k = rint(t * 1.4426950408889634), r = (t - k * 0.6931471803691238) - k * 1.9082149292705877e-10, the degree-13 Taylor
+ * polynomial of exp(r) by Horner over the literals 1 / k!, times 2^k built from its bit pattern.  No maths-library call:
+ * the result is tests/frangi_reference.py's, bit for bit.
+ *   g_dev    [h, w] binary64, row stride ldg
+ *   out_dev  [h, w] binary64, row stride ldo; read unless `first`; must not overlap g
+ *   scale    applied after the maximum: 1.0 except on the last scale of a fold
+ * h, w >= 2 (np.gradient's demand).  Null or misaligned pointers, h or w < 2, strides < w, s2 / bsq / gsq not finite or
+ * not > 0, out overlapping g: PXSOM_ERR_INVALID_ARG before any HIP call; h * w > 2^31 - 1 or h > 4 * 65535:
+ * PXSOM_ERR_UNSUPPORTED.  No atomics, no workspace: the same input gives the same bits on every run. */
+int pxsom_frangi_scale(const double *g_dev, int64_t ldg, int h, int w, double s2, double bsq, double gsq, int first,
+                       double scale, double *out_dev, int64_t ldo, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
