@@ -164,6 +164,10 @@ SYMBOLS = {
     "pxsom_sobel_magnitude": (_i32, [_vp, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
     "pxsom_class_markers": (_i32, [_vp, _i32, _i32, _i64, _f64, _f64, _vp, _i64, _vp]),
     "pxsom_frangi_scale": (_i32, [_vp, _i64, _i32, _i32, _f64, _f64, _f64, _i32, _f64, _vp, _i64, _vp]),
+    "pxsom_plane_divide": (_i32, [_vp, _i32, _i32, _i64, _f64, _vp, _i64, _vp]),
+    "pxsom_clahe_quantize": (_i32, [_vp, _i32, _i32, _i64, _f64, _f64, _vp, _i64, _vp]),
+    "pxsom_clahe_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "pxsom_clahe_equalize": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _f64, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
 }
 
 _lib = None

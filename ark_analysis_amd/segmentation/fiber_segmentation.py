@@ -31,7 +31,15 @@ pxsom_gaussian_blur_plane_mode and pxsom_frangi_scale, one of each per width.  T
 the numpy statement of tests/frangi_reference.py bit for bit, including its own exponential; parity with skimage itself
 is not pinned.
 
-Not built: ``equalize_adapthist`` before ``frangi``, and ``watershed`` after the middle.
+Also built: the front -- :func:`contrast_adjusted_channel`, ``equalize_adapthist(b / np.max(b),
+kernel_size=fov_len / contrast_scaling_divisor)`` with ``b = gaussian_filter(image, sigma=blur)`` in skimage 0.19's
+statement as recalled (2^14 grey levels, 256 bins of 65, clipped tile histograms, four-tile interpolation in float32), and
+:func:`fiber_watershed_inputs_from_channel`, which runs the front, the ridge filter and the K25 middle as one chain on
+the device.  On the device: pxsom_gaussian_blur_plane_mode, pxsom_plane_minmax, pxsom_plane_divide, pxsom_clahe_quantize
+and pxsom_clahe_equalize.  The result equals the numpy statement of tests/clahe_reference.py bit for bit; parity with
+skimage itself is not pinned.
+
+Not built: ``watershed`` after the middle.
 :func:`segment_fibers`, :func:`run_fiber_segmentation` and :func:`plot_fiber_segmentation_steps` keep
 the reference's signatures, validate their paths and the channel as the reference does, and then raise
 NotImplementedError."""
@@ -276,6 +284,97 @@ def fiber_watershed_inputs_from_contrast(contrast_adjusted, fiber_widths=range(1
     ridges = np.asarray(ridges, dtype=np.float64)
     _write_debug(out_dir, fov, debug, frangi_filter=ridges, thresholded=got.markers, ridges_thresholded=got.distance_transformed)
     return got, ridges
+
+
+# ---- the contrast-adjusted channel (K27) ---------------------------------------------------------------------------------
+def _contrast_device(channel: np.ndarray, blur: float, kernel_size: float, clip_limit: float) -> np.ndarray:
+    """som_device.contrast_adjust on a host ``[H, W]`` float64 plane: the host array ``equalize_adapthist(b / b.max(),
+    kernel_size, clip_limit)`` with ``b = gaussian_filter(channel, blur)``."""
+    import torch
+    from .. import _capi, som_device
+    plane = torch.from_numpy(np.array(channel, dtype=np.float64, order="C")).to(_capi.require_gpu())
+    return som_device.contrast_adjust(plane, blur, kernel_size, clip_limit).cpu().numpy()
+
+
+def _channel_watershed_inputs_device(channel: np.ndarray, blur: float, kernel_size: float, sigmas, ridge_cutoff: float,
+                                     sobel_blur: float, thresholds):
+    """som_device.channel_watershed_inputs on a host ``[H, W]`` float64 plane, one upload and one chain on the device:
+    host arrays ``(contrast, ridges, dist, (t0, t1), markers, elevation)``."""
+    import torch
+    from .. import _capi, som_device
+    plane = torch.from_numpy(np.array(channel, dtype=np.float64, order="C")).to(_capi.require_gpu())
+    contrast, ridges, dist, t, markers, elevation = som_device.channel_watershed_inputs(plane, blur, kernel_size, sigmas,
+                                                                                        ridge_cutoff, sobel_blur, thresholds)
+    return contrast.cpu().numpy(), ridges.cpu().numpy(), dist.cpu().numpy(), t, markers.cpu().numpy(), elevation.cpu().numpy()
+
+
+CLAHE_CLIP_LIMIT = 0.01                                       # equalize_adapthist's default, which the reference keeps
+
+
+def _channel_arguments(image, blur, contrast_scaling_divisor):
+    """The checked front arguments, without a device: ``(channel float64, blur, kernel_size)`` with ``kernel_size =
+    image.shape[0] / contrast_scaling_divisor``, as the reference computes it from ``fov_len``."""
+    from ..som_device.planes import check_blur_sigma, clahe_arguments
+    image = np.asarray(image)
+    if image.ndim != 2 or image.size == 0:
+        raise ValueError("image must be a non-empty [H, W] array, got shape %s" % (image.shape,))
+    divisor = float(contrast_scaling_divisor)
+    if not (np.isfinite(divisor) and divisor > 0):
+        raise ValueError("contrast_scaling_divisor must be finite and > 0, got %r" % (contrast_scaling_divisor,))
+    blur = float(blur)
+    if not (np.isfinite(blur) and blur >= 0):
+        raise ValueError("blur must be finite and >= 0, got %r" % (blur,))
+    check_blur_sigma(blur)
+    kernel_size = image.shape[0] / divisor
+    clahe_arguments(image.shape, kernel_size, CLAHE_CLIP_LIMIT)
+    channel = image.astype(np.float64)
+    if not np.isfinite(channel).all():
+        raise ValueError("image must be finite: the reference's division by the maximum gives NaNs otherwise")
+    if not channel.max() > 0:
+        raise ValueError("image must hold a positive pixel: the reference divides the blurred image by its maximum")
+    return channel, blur, kernel_size
+
+
+def contrast_adjusted_channel(image, blur=2, contrast_scaling_divisor=128, out_dir=None, fov=None, debug=False):
+    """The front of ``segment_fibers``: ``equalize_adapthist(b / np.max(b), kernel_size=image.shape[0] /
+    contrast_scaling_divisor)`` with ``b = gaussian_filter(image, sigma=blur)`` of a ``[H, W]`` plane (taken as float64;
+    ``H, W >= 2``) as a float64 host array in [0, 1] -- the reference's ``contrast_adjusted``.  skimage 0.19's statement as
+    recalled (parity with skimage itself is unpinned); the plane blur, pxsom_plane_minmax,
+    pxsom_plane_divide, pxsom_clahe_quantize and pxsom_clahe_equalize on the device.  With ``debug`` and ``out_dir`` (and
+    ``fov``) the reference's debug file of this stage is written: ``_debug/<fov>_contrast_adjusted.tiff``, as float32 --
+    the reference saves a float64 plane, which image_io.write_image does not write; the plane is rounded once.
+    ValueError: a kernel size below 1 (the reference divides by zero there), a divisor that is not finite and positive,
+    a ``blur`` that is not finite or negative, an image with a pixel that is not finite or without a positive pixel, a
+    blurred image whose maximum is not positive; NotImplementedError: a kernel size beyond the shorter side, a ``blur`` beyond the
+    device blur's radius."""
+    channel, blur, kernel_size = _channel_arguments(image, blur, contrast_scaling_divisor)
+    _check_debug(out_dir, fov, debug)
+    contrast = np.asarray(_contrast_device(channel, blur, kernel_size, CLAHE_CLIP_LIMIT), dtype=np.float64)
+    _write_debug(out_dir, fov, debug, contrast_adjusted=contrast)
+    return contrast
+
+
+def fiber_watershed_inputs_from_channel(image, blur=2, contrast_scaling_divisor=128, fiber_widths=range(1, 10, 2),
+                                        ridge_cutoff=0.1, sobel_blur=1, out_dir=None, fov=None, debug=False):
+    """``segment_fibers`` from the raw channel to what ``watershed`` receives, as one chain on the device:
+    :func:`contrast_adjusted_channel`, :func:`frangi_ridges` (the reference's defaults, ``* 10000``) and
+    :func:`fiber_watershed_inputs` without a plane crossing to the host in between.  Returns ``(inputs, ridges,
+    contrast_adjusted)``: the ``WatershedInputs`` and two float64 planes.  With ``debug`` and ``out_dir`` (and ``fov``)
+    the four debug files of these stages are written (``_debug/<fov>_contrast_adjusted.tiff``, ``_frangi_filter.tiff``,
+    ``_thresholded.tiff``, ``_ridges_thresholded.tiff``, float32).  Errors: those of the three functions."""
+    from ..som_device.planes import check_blur_sigma, frangi_arguments
+    channel, blur, kernel_size = _channel_arguments(image, blur, contrast_scaling_divisor)
+    sigmas, _, _ = frangi_arguments(fiber_widths, 0.5, 15)
+    check_blur_sigma(sobel_blur)
+    _check_debug(out_dir, fov, debug)
+    contrast, ridges, dist, t, markers, elevation = _channel_watershed_inputs_device(
+        channel, blur, kernel_size, sigmas, float(ridge_cutoff), sobel_blur, threshold_multiotsu_from_histogram)
+    got = WatershedInputs(np.asarray(dist, dtype=np.float64), np.asarray(t, dtype=np.float64),
+                          np.asarray(markers, dtype=np.int32), np.asarray(elevation, dtype=np.int32))
+    contrast, ridges = np.asarray(contrast, dtype=np.float64), np.asarray(ridges, dtype=np.float64)
+    _write_debug(out_dir, fov, debug, contrast_adjusted=contrast, frangi_filter=ridges, thresholded=got.markers,
+                 ridges_thresholded=got.distance_transformed)
+    return got, ridges, contrast
 
 
 # ---- the object table -------------------------------------------------------------------------------------------------

@@ -704,3 +704,122 @@ def ridge_watershed_inputs(contrast: torch.Tensor, sigmas=FRANGI_SIGMAS, ridge_c
     ridge map stays in HBM."""
     ridges = frangi(contrast, sigmas, beta, gamma, scale=10000.0)
     return (ridges,) + tuple(watershed_inputs(ridges, ridge_cutoff, sobel_blur, thresholds))
+
+
+# ---- fibre segmentation: adaptive histogram equalisation, the front (K27) -------------------------------------------------
+CLAHE_GREY_LEVELS = 2 ** 14                          # skimage's NR_OF_GRAY
+CLAHE_NBINS = 256                                    # kBins of csrc/pxsom_clahe.hip
+
+
+def clahe_arguments(shape, kernel_size, clip_limit=0.01, nbins=256):
+    """The checked arguments of :func:`equalize_adapthist` for a plane of ``shape``, without a device: ``(k, clim,
+    map_scale)`` -- the tile side ``int(kernel_size)``, the clip limit in counts (``int(clip(clip_limit * k * k, 1,
+    None))``, or 2^14 for ``clip_limit <= 0``: no clipping) and ``16383 / (k * k)`` in a host double.  ValueError: a shape
+    that is not ``(H, W)`` with ``H, W >= 2``, a kernel size that is not finite or below 1 (the reference divides by zero
+    there), a ``clip_limit`` that is not finite.  NotImplementedError: ``nbins`` other than 256, a kernel size that is
+    not a scalar (None, skimage's data-dependent default, among them), one beyond ``min(H, W)``."""
+    shape = tuple(shape)
+    if len(shape) != 2 or min(shape) < 2:
+        raise ValueError("equalize_adapthist takes a [H, W] plane with H, W >= 2, got shape %s" % (shape,))
+    if isinstance(nbins, (bool, np.bool_)) or nbins != CLAHE_NBINS:
+        raise NotImplementedError("equalize_adapthist: nbins=%r; only 256 bins are implemented" % (nbins,))
+    if kernel_size is None or np.ndim(kernel_size) != 0:
+        raise NotImplementedError("equalize_adapthist: kernel_size=%r; only a scalar kernel size is implemented"
+                                  % (kernel_size,))
+    if not np.isfinite(float(kernel_size)) or int(kernel_size) < 1:
+        raise ValueError("equalize_adapthist: kernel_size=%r must be finite and at least 1" % (kernel_size,))
+    k = int(kernel_size)
+    if k > min(shape):
+        raise NotImplementedError("equalize_adapthist: kernel_size %d beyond the shorter side of a %d x %d plane is not "
+                                  "implemented" % (k, shape[0], shape[1]))
+    clip_limit = float(clip_limit)
+    if not np.isfinite(clip_limit):
+        raise ValueError("equalize_adapthist: clip_limit must be finite, got %r" % (clip_limit,))
+    ke = k * k
+    clim = int(np.clip(clip_limit * ke, 1, None)) if clip_limit > 0.0 else CLAHE_GREY_LEVELS
+    return k, clim, (CLAHE_GREY_LEVELS - 1) / ke
+
+
+def _check_apart(out: torch.Tensor, plane: torch.Tensor, why: str) -> None:
+    lo, hi = _byte_range(out)
+    plo, phi = _byte_range(plane)
+    if lo < phi and plo < hi:
+        raise ValueError("out must not share memory with the input: " + why)
+
+
+def _equalize_gray(gray: torch.Tensor, k: int, clim: int, map_scale: float, out, maps_out, raw_out) -> torch.Tensor:
+    """pxsom_clahe_equalize on a uint16 ``[H, W]`` HBM plane of grey levels; ``out`` is the caller's checked plane."""
+    h, w = gray.shape
+    nty, ntx = -(-h // k), -(-w // k)
+    if maps_out is not None and (maps_out.shape != (nty, ntx, CLAHE_NBINS) or maps_out.dtype != torch.uint16 or not maps_out.is_cuda
+                                 or not maps_out.is_contiguous()):
+        raise ValueError("maps_out must be a contiguous [%d, %d, 256] uint16 HBM tensor" % (nty, ntx))
+    if raw_out is not None:
+        _rows_plane(raw_out, h, w, torch.uint16, gray.device, "raw_out")
+    for name, t in (("out", out), ("maps_out", maps_out), ("raw_out", raw_out)):
+        if t is not None and t.device != gray.device:
+            raise ValueError("%s must be on the plane's device" % name)
+    wsb = _capi.lib().pxsom_clahe_workspace_bytes(h, w, k)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=gray.device)
+    _capi.call("pxsom_clahe_equalize", gray.data_ptr(), h, w, _ld(gray), k, min(clim, 2 ** 31 - 1), map_scale, out.data_ptr(),
+               _ld(out), None if maps_out is None else maps_out.data_ptr(), None if raw_out is None else raw_out.data_ptr(),
+               w if raw_out is None else _ld(raw_out), ws.data_ptr(), wsb, _capi.stream_ptr())
+    return out
+
+
+def equalize_adapthist(plane: torch.Tensor, kernel_size, clip_limit=0.01, nbins=256, out: Optional[torch.Tensor] = None,
+                       lo_hi=None, maps_out: Optional[torch.Tensor] = None, raw_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``skimage.exposure.equalize_adapthist(plane, kernel_size, clip_limit, nbins=256)`` in skimage 0.19's statement as
+    recalled (include/pxsom.h "K27"; parity with skimage itself is unpinned) of a ``[H, W]`` float64 HBM plane (rows
+    contiguous, any row stride; ``H, W >= 2``) -> float64 ``[H, W]`` in [0, 1] in HBM (``out`` if given: rows contiguous,
+    any row stride, not sharing memory with the plane).  pxsom_clahe_quantize turns the plane into 2^14 grey levels over
+    its own minimum and maximum; pxsom_clahe_equalize builds the clipped tile maps, interpolates and rescales, its minimum
+    and maximum never leaving the device.  One host synchronisation at most: :func:`plane_minmax`, skipped when the caller
+    has ``lo_hi = (min, max)``.  ``maps_out`` (uint16 ``[ceil(H / k), ceil(W / k), 256]``, contiguous) and ``raw_out``
+    (uint16 ``[H, W]``, rows contiguous) receive the tile maps and the interpolated plane before the last rescale.  The
+    arguments are those of :func:`clahe_arguments`; ValueError for a plane that holds a NaN or an infinity."""
+    h, w, ld = _f64_plane(plane, "plane")
+    k, clim, map_scale = clahe_arguments((h, w), kernel_size, clip_limit, nbins)
+    out = _rows_plane(out, h, w, torch.float64, plane.device, "out")
+    _check_apart(out, plane, "the result is written while the caller may still hold the plane")
+    lo, hi = plane_minmax(plane) if lo_hi is None else (float(lo_hi[0]), float(lo_hi[1]))
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+        raise ValueError("equalize_adapthist takes a finite plane, its range is [%r, %r]" % (lo, hi))
+    gray = torch.empty((h, w), dtype=torch.uint16, device=plane.device)
+    _capi.call("pxsom_clahe_quantize", plane.data_ptr(), h, w, ld, lo, hi, gray.data_ptr(), w, _capi.stream_ptr())
+    return _equalize_gray(gray, k, clim, map_scale, out, maps_out, raw_out)
+
+
+def contrast_adjust(channel: torch.Tensor, blur=2.0, kernel_size=8, clip_limit=0.01, out: Optional[torch.Tensor] = None,
+                    maps_out: Optional[torch.Tensor] = None, raw_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The front of ``segment_fibers`` on a contiguous ``[H, W]`` float64 HBM plane (``H, W >= 2``):
+    ``b = gaussian_filter(channel, blur)`` (:func:`gaussian_blur_plane_mode`, reflect), ``b / b.max()``
+    (pxsom_plane_divide, in place) and :func:`equalize_adapthist` of it -> float64 ``[H, W]`` in [0, 1] in HBM.  One
+    :func:`plane_minmax` of the blurred plane serves the division and the first rescale: division by a positive number
+    is monotone, so the divided plane's range is ``[min / max, 1.0]``.  ValueError for a NaN in the blurred plane or a
+    maximum that is not finite and positive (the reference produces NaNs there); otherwise the errors of
+    :func:`clahe_arguments` and the plane blur."""
+    if channel.dim() != 2 or not channel.is_cuda or channel.dtype != torch.float64 or not channel.is_contiguous() or not channel.numel():
+        raise ValueError("channel must be a non-empty contiguous 2-D float64 HBM tensor")
+    h, w = channel.shape
+    k, clim, map_scale = clahe_arguments((h, w), kernel_size, clip_limit)
+    check_blur_sigma(blur)
+    out = _rows_plane(out, h, w, torch.float64, channel.device, "out")
+    _check_apart(out, channel, "the result is written while the caller may still hold the channel")
+    b = gaussian_blur_plane_mode(channel, blur, "reflect")
+    lo, hi = plane_minmax(b)
+    if not (np.isfinite(hi) and hi > 0.0 and np.isfinite(lo)):
+        raise ValueError("contrast_adjust: the blurred channel's range [%r, %r] must be finite with a positive maximum" % (lo, hi))
+    _capi.call("pxsom_plane_divide", b.data_ptr(), h, w, w, hi, b.data_ptr(), w, _capi.stream_ptr())
+    gray = torch.empty((h, w), dtype=torch.uint16, device=channel.device)
+    _capi.call("pxsom_clahe_quantize", b.data_ptr(), h, w, w, lo / hi, 1.0, gray.data_ptr(), w, _capi.stream_ptr())
+    return _equalize_gray(gray, k, clim, map_scale, out, maps_out, raw_out)
+
+
+def channel_watershed_inputs(channel: torch.Tensor, blur=2.0, kernel_size=8, sigmas=FRANGI_SIGMAS, ridge_cutoff: float = 0.1,
+                             sobel_blur: float = 1, thresholds=None, clip_limit=0.01, beta=0.5, gamma=15.0):
+    """The device chain of ``segment_fibers`` from the raw channel (a contiguous ``[H, W]`` float64 HBM plane) to what
+    ``watershed`` receives: :func:`contrast_adjust`, then :func:`ridge_watershed_inputs` on its result.  Returns
+    ``(contrast, ridges, dist, (t0, t1), markers, elevation)``; every plane stays in HBM."""
+    contrast = contrast_adjust(channel, blur, kernel_size, clip_limit)
+    return (contrast,) + tuple(ridge_watershed_inputs(contrast, sigmas, ridge_cutoff, sobel_blur, thresholds, beta, gamma))

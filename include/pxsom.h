@@ -1102,6 +1102,51 @@ int pxsom_class_markers(const double *dist_dev, int h, int w, int64_t ld, double
 int pxsom_frangi_scale(const double *g_dev, int64_t ldg, int h, int w, double s2, double bsq, double gsq, int first,
                        double scale, double *out_dev, int64_t ldo, void *stream);
 
+/* ---- fibre segmentation, adaptive histogram equalisation (K27) ------------------------------------------------------------
+ * reference: ark/segmentation/fiber_segmentation.py segment_fibers, its front:
+ *   blurred = gaussian_filter(channel, sigma=blur);  contrast_adjusted = equalize_adapthist(blurred / np.max(blurred),
+ *   kernel_size=fov_len / contrast_scaling_divisor)
+ * in skimage 0.19's statement of equalize_adapthist for a 2-D plane, a scalar kernel size k and 256 bins, as recalled
+ * (tests/clahe_reference.py is the same statement in numpy; parity with skimage itself is unpinned).  The blur is
+ * pxsom_gaussian_blur_plane_mode, its maximum pxsom_plane_minmax.  Symbols added under ABI 9, none changed.  Planes are
+ * [h, w] with contiguous rows and a row stride in elements.
+ *
+ * pxsom_plane_divide: out = plane / divisor in binary64 (the division by the maximum); out may be the plane itself (same
+ * pointer and stride) or must not overlap it.
+ *
+ * pxsom_clahe_quantize: rescale_intensity to the 2^14 grey levels.  With lo, hi the plane's minimum and maximum:
+ *   lo != hi:  gray = uint16(rint((clip(v, lo, hi) - lo) / (hi - lo) * 16383 + 0))        (rint: half to even)
+ *   lo == hi:  gray = uint16(rint(clip(v, 0, 16383)))                                       (the constant-plane rule)
+ * in binary64 without contraction.  A NaN pixel gives 0.
+ *
+ * pxsom_clahe_equalize: gray [h, w] uint16 in 0 .. 16383 -> out [h, w] binary64 in [0, 1].
+ *   tile (ty, tx), ty < nty = ceil(h / k), tx < ntx = ceil(w / k), covers rows [ty k, (ty + 1) k) and the columns alike;
+ *     an index i >= S of an axis of length S is read at 2 (S - 1) - i (numpy's 'reflect' pad; k <= S: one reflection)
+ *   hist[256] of gray / 65 over the tile;  clip_histogram(hist, min(clim, k k)) as the statement has it, loop and all
+ *   map[b] = int(min(cumsum(hist)[b] * map_scale + 0, 16383)), map_scale = 16383 / (k k) from the host, binary64
+ *   pixel (y, x): p = y + k / 2, b = p / k, j = p % k; rows of tiles clamp(b - 1), clamp(b) in [0, nty - 1] with weights
+ *     1 - j / k, j / k (binary64); columns alike; raw = uint16(float32 sum over (0,0), (0,1), (1,0), (1,1), in this order,
+ *     of float32(double(map[tile][gray / 65]) * (row weight * column weight))), truncated
+ *   out = (raw - min) / (max - min) over the plane's own minimum and maximum, which stay on the device (integer atomics);
+ *     min == max: out = clip(raw, 0, 1)
+ *   maps_out_dev  [nty, ntx, 256] uint16, 8-byte aligned, or NULL: receives the tile maps
+ *   raw_out_dev   [h, w] uint16, row stride ld_raw, or NULL: receives raw
+ *   workspace     pxsom_clahe_workspace_bytes(h, w, k) bytes (0 for refused sizes), 16-byte aligned
+ * A grey value above 16383 is counted in, and mapped through, bin 255: no access leaves the buffers.
+ *
+ * Null or misaligned pointers, h or w < 2, strides < w, k < 1 or k > min(h, w), clim < 1, lo, hi or map_scale not finite,
+ * lo > hi, map_scale <= 0, a divisor that is 0 or not finite, buffers that overlap, a short workspace:
+ * PXSOM_ERR_INVALID_ARG before any HIP call; h * w > 2^31 - 1 or h > 4 * 65535: PXSOM_ERR_UNSUPPORTED.  Integer atomics
+ * only: the same input gives the same bits on every run. */
+int pxsom_plane_divide(const double *plane_dev, int h, int w, int64_t ld, double divisor, double *out_dev, int64_t ldo,
+                       void *stream);
+int pxsom_clahe_quantize(const double *src_dev, int h, int w, int64_t ld, double lo, double hi, uint16_t *gray_dev,
+                         int64_t ld_gray, void *stream);
+size_t pxsom_clahe_workspace_bytes(int h, int w, int k);
+int pxsom_clahe_equalize(const uint16_t *gray_dev, int h, int w, int64_t ld, int k, int clim, double map_scale,
+                         double *out_dev, int64_t ld_out, uint16_t *maps_out_dev, uint16_t *raw_out_dev, int64_t ld_raw,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
