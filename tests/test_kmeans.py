@@ -271,6 +271,35 @@ def test_entry_point_checks_and_the_grouping_rule():
     assert som_device.kmeans_group_count(1, [1] * 33) == 2              # at most 32 problems share a group
 
 
+def test_group_count_equals_the_python_rule_on_seeded_draws():
+    """pxsom_kmeans_group_count against the rule restated in tests/kmeans_edge_cases.py: lists on both sides of the
+    32-problem limit, lists that sit on the byte budget, and 300 seeded (d, k list) draws of up to 70 problems."""
+    from ark_analysis_amd import som_device
+    from tests import kmeans_edge_cases as ec
+    for count in (31, 32, 33, 63, 64, 65, 70):              # the limit alone: 32 of them are 10432 bytes
+        assert som_device.kmeans_group_count(1, [1] * count) == len(ec.groups(1, [1] * count)) == -(-count // 32)
+    # the bytes alone, one centre either side of the budget (no d and k list fill 65536 to the byte)
+    assert ec.group_bytes(124, 4, 64) == 65384 and ec.group_bytes(125, 4, 64) == 65902
+    assert som_device.kmeans_group_count(64, [32, 32, 32, 28]) == len(ec.groups(64, [32, 32, 32, 28])) == 1
+    assert som_device.kmeans_group_count(64, [32, 32, 32, 29]) == len(ec.groups(64, [32, 32, 32, 29])) == 2
+    rs = np.random.RandomState(19)
+    seen = set()
+    for draw in range(300):
+        d = int(rs.choice([1, 3, 4, 5, 17, 32, 33, 60, 61, 64]))
+        count = int(rs.randint(1, 71))
+        top = int(rs.choice([1, 2, 8, 32]))                 # small k: the problem limit closes; large k: the bytes do
+        ks = rs.randint(1, top + 1, size=count).tolist()
+        want = ec.groups(d, ks)
+        assert som_device.kmeans_group_count(d, ks) == len(want), (d, ks)
+        assert sorted(p for g in want for p in g) == list(range(count))
+        for g, nxt in zip(want, want[1:]):
+            fits = ec.group_bytes(sum(ks[p] for p in g) + ks[nxt[0]], len(g) + 1, d) <= ec.LDS_BUDGET
+            assert not fits or len(g) == ec.MAX_GROUP
+            seen.add("limit" if fits else "bytes")
+        seen.add("one" if len(want) == 1 else "several")
+    assert seen == {"limit", "bytes", "one", "several"}    # the draws close groups both ways, and leave some whole
+
+
 def test_device_entry_point_is_loud_without_gpu():
     import torch
     if torch.cuda.is_available():
