@@ -168,6 +168,8 @@ SYMBOLS = {
     "pxsom_clahe_quantize": (_i32, [_vp, _i32, _i32, _i64, _f64, _f64, _vp, _i64, _vp]),
     "pxsom_clahe_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "pxsom_clahe_equalize": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _f64, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "pxsom_watershed_workspace_bytes": (_sz, [_i32, _i32]),
+    "pxsom_watershed": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp, _vp]),
 }
 
 _lib = None

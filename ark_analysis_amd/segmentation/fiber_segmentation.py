@@ -39,10 +39,21 @@ the device.  On the device: pxsom_gaussian_blur_plane_mode, pxsom_plane_minmax, 
 and pxsom_clahe_equalize.  The result equals the numpy statement of tests/clahe_reference.py bit for bit; parity with
 skimage itself is not pinned.
 
+Also built: the stage between the middle and the tail -- :func:`watershed_labels`,
+``watershed(elevation_map, markers)`` at skimage 0.19's defaults as recalled (``RECALLED_WATERSHED``; pxsom_watershed, the
+priority flood computed in parallel rounds) -- and with it the whole of ``segment_fibers`` on one channel plane:
+:func:`segment_fiber_channel` does the job of ``segment_fibers`` from its ``fiber_channel_data`` line to its return (the
+labels file, the four debug files, the object table), and :func:`run_fiber_channel_segmentation` the job of
+``run_fiber_segmentation`` (every FOV folder in natural order, the alignment score, ``fiber_object_table.csv``).  The
+channel goes up once and the filtered labels come down; no plane crosses in between.  Parity with skimage itself is not
+pinned.
+
+The three entries that carry the reference's own names have not been switched over to these yet, and read as before K28:
 Not built: ``watershed`` after the middle.
-:func:`segment_fibers`, :func:`run_fiber_segmentation` and :func:`plot_fiber_segmentation_steps` keep
-the reference's signatures, validate their paths and the channel as the reference does, and then raise
-NotImplementedError."""
+:func:`segment_fibers` (which takes an xarray), :func:`run_fiber_segmentation` and :func:`plot_fiber_segmentation_steps`
+keep the reference's signatures, validate their paths and the channel as the reference does, and then raise
+NotImplementedError; call :func:`segment_fiber_channel` and :func:`run_fiber_channel_segmentation` instead (the plots are
+not built)."""
 import os
 from collections import namedtuple
 from typing import Dict, Optional
@@ -139,6 +150,14 @@ RECALLED_MULTIOTSU = {"prob": "float64", "tie": "first", "exact_bins": "occupied
 MULTIOTSU_CHOICES = {"prob": ("float64", "float32"), "tie": ("first", "last"), "exact_bins": ("occupied", "search"),
                      "few_bins": ("raise", "search")}
 MULTIOTSU_FEW_VALUES = ("The input image has only %d different values. It cannot be thresholded in %d classes.")
+# The same for skimage 0.19's watershed(image, markers) at its defaults; the device is built for the defaults.
+#   marker_ties  "raster": markers of one value are popped in raster order; "reverse": in reverse raster order.  skimage
+#                gives every marker age 0 and leaves equal keys to its binary heap.
+#   neighbours   the order in which a popped pixel visits its 4-neighbours.  Under a (value, age) key no label depends on
+#                it (every pixel one pop pushes carries one label, and stays together in every queue): recorded because
+#                the statement has to choose one.
+RECALLED_WATERSHED = {"marker_ties": "raster", "neighbours": "-W,-1,+1,+W"}
+WATERSHED_CHOICES = {"marker_ties": ("raster", "reverse"), "neighbours": ("-W,-1,+1,+W", "+W,+1,-1,-W")}
 
 
 def threshold_multiotsu_from_histogram(counts, edges, classes=3, recalled=None):
@@ -601,6 +620,117 @@ def generate_summary_stats(fiber_object_table, fibseg_dir, tile_length=512, min_
     fov_stats.to_csv(os.path.join(fibseg_dir, "fiber_stats_table.csv"), index=False)
     tile_stats.to_csv(os.path.join(tile_dir, "fiber_stats_table-tile_%s.csv" % tile_length), index=False)
     return fov_stats, tile_stats
+
+
+# ---- the watershed, and segment_fibers end to end on one channel plane (K28) ---------------------------------------------
+def _watershed_device(elevation: np.ndarray, markers: np.ndarray) -> np.ndarray:
+    """som_device.watershed on two host ``[H, W]`` int32 planes: the int32 labels on the host."""
+    import torch
+    from .. import _capi, som_device
+    gpu = _capi.require_gpu()
+    planes = [torch.from_numpy(np.array(a, dtype=np.int32, order="C")).to(gpu) for a in (elevation, markers)]
+    return som_device.watershed(planes[0], planes[1]).cpu().numpy()
+
+
+def _channel_fiber_labels_device(channel: np.ndarray, blur: float, kernel_size: float, sigmas, ridge_cutoff: float,
+                                 sobel_blur: float, thresholds, min_fiber_size: int, planes: bool):
+    """som_device.channel_fiber_labels on a host ``[H, W]`` float64 plane, one upload and one chain on the device: the host
+    arrays ``(labels, contrast, ridges, dist, (t0, t1), markers, elevation)``.  Only the int32 labels and the two
+    thresholds come down unless ``planes`` (the debug files) asks for the rest, which is None otherwise."""
+    import torch
+    from .. import _capi, som_device
+    plane = torch.from_numpy(np.array(channel, dtype=np.float64, order="C")).to(_capi.require_gpu())
+    labels, contrast, ridges, dist, t, markers, elevation = som_device.channel_fiber_labels(
+        plane, blur, kernel_size, sigmas, ridge_cutoff, sobel_blur, thresholds, min_fiber_size)
+    rest = [p.cpu().numpy() if planes else None for p in (contrast, ridges, dist, markers, elevation)]
+    return labels.cpu().numpy(), rest[0], rest[1], rest[2], t, rest[3], rest[4]
+
+
+def watershed_labels(elevation, markers):
+    """``skimage.segmentation.watershed(elevation, markers)`` at its defaults (connectivity 1, no mask, no compactness, no
+    watershed line) of two ``[H, W]`` arrays, each taken ``.astype(np.int32)`` as the reference passes them: the int32
+    labels on the host.  skimage 0.19's statement as recalled (``RECALLED_WATERSHED``; parity with skimage
+    itself is unpinned): a priority flood keyed (value, age), markers of one value in raster order; any non-zero marker is
+    a label, and a plane without one comes back all zeros.  ValueError: planes that are not 2-D, empty, or of two shapes,
+    and values that an int32 does not hold (NaN among them)."""
+    planes = []
+    for name, a in (("elevation", elevation), ("markers", markers)):
+        a = np.asarray(a)
+        if a.ndim != 2 or a.size == 0:
+            raise ValueError("%s must be a non-empty [H, W] array, got shape %s" % (name, a.shape))
+        if a.dtype.kind not in "biuf":
+            raise ValueError("%s must be numeric, got %s" % (name, a.dtype))
+        if a.dtype.kind == "f" and not np.isfinite(a).all():
+            raise ValueError("%s must be finite" % name)
+        if a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1:
+            raise ValueError("%s holds values beyond int32" % name)
+        planes.append(a.astype(np.int32))
+    if planes[0].shape != planes[1].shape:
+        raise ValueError("elevation and markers must have one shape, got %s and %s" % (planes[0].shape, planes[1].shape))
+    return np.asarray(_watershed_device(planes[0], planes[1]), dtype=np.int32)
+
+
+def segment_fiber_channel(image, fov, out_dir, blur=2, contrast_scaling_divisor=128, fiber_widths=range(1, 10, 2),
+                          ridge_cutoff=0.1, sobel_blur=1, min_fiber_size=15, object_properties=FIBER_OBJECT_PROPS,
+                          save_csv=True, debug=False):
+    """The reference's ``segment_fibers`` from its ``fiber_channel_data`` line to its return, on the channel plane itself:
+    ``image`` is the ``[H, W]`` fibre channel of ``fov`` (taken as float64), where the reference takes an xarray and a
+    channel name.  One chain on the device -- the front (K27), frangi (K26), the middle (K25), the watershed (K28), the
+    pixels of marker class 2, ``ndi.label`` and the ``min_fiber_size`` filter (K23) -- then ``<fov>_fiber_labels.tiff``
+    (int32) in ``out_dir``, with ``debug`` the four files of ``_debug/`` (float32, as :func:`fiber_watershed_inputs`
+    explains), :func:`fiber_object_props` and, with ``save_csv``, ``fiber_object_table.csv`` written with its index, as the
+    reference writes it.  Returns the table.  Errors: a missing ``out_dir`` (FileNotFoundError), an unbuilt property
+    (NotImplementedError) and those of :func:`fiber_watershed_inputs_from_channel`, all before any device work."""
+    from ..som_device.planes import check_blur_sigma, frangi_arguments
+    _object_columns(object_properties)
+    validate_paths(out_dir)
+    channel, blur, kernel_size = _channel_arguments(image, blur, contrast_scaling_divisor)
+    sigmas, _, _ = frangi_arguments(fiber_widths, 0.5, 15)
+    check_blur_sigma(sobel_blur)
+    labels, contrast, ridges, dist, _, markers, _ = _channel_fiber_labels_device(
+        channel, blur, kernel_size, sigmas, float(ridge_cutoff), sobel_blur, threshold_multiotsu_from_histogram,
+        int(min_fiber_size), bool(debug))
+    labels = np.asarray(labels, dtype=np.int32)
+    if debug:
+        _write_debug(out_dir, fov, True, thresholded=np.asarray(markers), ridges_thresholded=np.asarray(dist),
+                     frangi_filter=np.asarray(ridges), contrast_adjusted=np.asarray(contrast))
+    image_io.write_image(os.path.join(out_dir, f"{fov}{_LABELS_SUFFIX}"), labels)
+    table = fiber_object_props(labels, fov, object_properties)
+    if save_csv:
+        table.to_csv(os.path.join(out_dir, "fiber_object_table.csv"))
+    return table
+
+
+def run_fiber_channel_segmentation(data_dir, fiber_channel, out_dir, img_sub_folder=None,
+                                   csv_compression: Optional[Dict[str, str]] = None, **kwargs):
+    """The reference's ``run_fiber_segmentation``: both folders must exist and the first FOV folder of ``data_dir`` (natural
+    order) must hold ``fiber_channel`` (FileNotFoundError, ValueError); then per FOV folder, in natural order, the channel's
+    image file is read (``<data_dir>/<fov>/<img_sub_folder>/<fiber_channel>.<ext>``) and :func:`segment_fiber_channel`
+    runs on it with ``save_csv=False`` and ``kwargs``.  The tables are stacked, scored by
+    :func:`calculate_fiber_alignment` when there is a row, written to ``fiber_object_table.csv`` without the index and
+    returned.  A cohort without a fibre gives the empty table with the object columns."""
+    sub = img_sub_folder or ""
+    validate_paths([data_dir, out_dir])
+    fovs = natsorted(list_folders(data_dir))
+    if len(fovs) == 0:
+        raise ValueError("no FOV folder in %s" % (data_dir,))
+    verify_in_list(fiber_channel=[fiber_channel],
+                   all_channels=remove_file_extensions(list_files(os.path.join(data_dir, fovs[0], sub))))
+    for name in ("save_csv", "fov", "out_dir", "image"):
+        if name in kwargs:
+            raise TypeError("run_fiber_channel_segmentation sets %s itself" % name)
+    tables = []
+    for fov in fovs:
+        files = list_files(os.path.join(data_dir, fov, sub), substrs=fiber_channel, exact_match=True)
+        if len(files) == 0:
+            raise ValueError("FOV %s holds no image of channel %s" % (fov, fiber_channel))
+        image = image_io.read_image(os.path.join(data_dir, fov, sub, files[0]))
+        tables.append(segment_fiber_channel(image, fov, out_dir, save_csv=False, **kwargs))
+    table = pd.concat(tables)
+    if len(table) > 0:
+        table = calculate_fiber_alignment(table)
+    table.to_csv(os.path.join(out_dir, "fiber_object_table.csv"), index=False, compression=csv_compression)
+    return table
 
 
 # ---- the entries whose front half is not built --------------------------------------------------------------------------

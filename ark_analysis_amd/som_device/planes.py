@@ -1,5 +1,6 @@
 """Image planes and masks: cluster and segmentation masks, the plane blurs, object masks (K16, K22), mask merging (K18),
-the distance map, histogram, markers and elevation of fibre segmentation (K25), its Frangi ridge filter (K26)."""
+the distance map, histogram, markers and elevation of fibre segmentation (K25), its Frangi ridge filter (K26), its
+adaptive histogram equalisation (K27) and its marker watershed (K28)."""
 import operator
 from typing import Optional
 
@@ -823,3 +824,65 @@ def channel_watershed_inputs(channel: torch.Tensor, blur=2.0, kernel_size=8, sig
     ``(contrast, ridges, dist, (t0, t1), markers, elevation)``; every plane stays in HBM."""
     contrast = contrast_adjust(channel, blur, kernel_size, clip_limit)
     return (contrast,) + tuple(ridge_watershed_inputs(contrast, sigmas, ridge_cutoff, sobel_blur, thresholds, beta, gamma))
+
+
+# ---- fibre segmentation: the marker watershed, and the chain to filtered labels (K28) ---------------------------------------
+WATERSHED_STATS = ("rounds", "levels", "descents", "labelled")     # the four int64 of pxsom_watershed's stats_host
+
+
+def _i32_plane(plane: torch.Tensor, what: str):
+    """``(h, w, ld)`` of a non-empty ``[H, W]`` int32 HBM plane with contiguous rows (any row stride)."""
+    if plane.dim() != 2 or not plane.is_cuda or plane.dtype != torch.int32:
+        raise ValueError("%s must be a 2-D int32 HBM tensor" % what)
+    h, w = plane.shape
+    if h == 0 or w == 0:
+        raise ValueError("%s must not be empty" % what)
+    if w > 1 and plane.stride(1) != 1:
+        raise ValueError("%s rows must be contiguous (stride(1) == 1)" % what)
+    return h, w, _ld(plane)
+
+
+def watershed(elevation: torch.Tensor, markers: torch.Tensor, out: Optional[torch.Tensor] = None, return_stats: bool = False):
+    """``skimage.segmentation.watershed(elevation, markers)`` at its defaults in skimage 0.19's statement as recalled
+    (include/pxsom.h "K28"; parity with skimage itself is unpinned) of two ``[H, W]`` int32 HBM planes (rows contiguous, any
+    row stride) -> int32 ``[H, W]`` labels in HBM (``out`` if given: rows contiguous, any row stride, sharing no memory with
+    the inputs).  Any non-zero marker is a label; without a marker the result is all zeros.  pxsom_watershed drives its
+    rounds from the host and synchronises once per round (a 40-byte read-back); no plane crosses.  With ``return_stats``
+    the result is ``(labels, stats)``, ``stats`` a dict of ``WATERSHED_STATS``: rounds, levels visited, rounds that took the
+    basin path, pixels the flood labelled."""
+    h, w, lde = _i32_plane(elevation, "elevation")
+    _, _, ldm = _i32_plane(markers, "markers")
+    if markers.shape != elevation.shape:
+        raise ValueError("elevation and markers must have one shape, got %s and %s" % (tuple(elevation.shape), tuple(markers.shape)))
+    if markers.device != elevation.device:
+        raise ValueError("markers must be on the elevation's device")
+    out = _label_plane(out, h, w, elevation.device, "out")
+    if out.device != elevation.device:
+        raise ValueError("out must be on the elevation's device")
+    for name, t in (("elevation", elevation), ("markers", markers)):
+        _check_apart(out, t, "the labels grow in out while %s is still read" % name)
+    wsb = _capi.lib().pxsom_watershed_workspace_bytes(h, w)
+    if wsb == 0:
+        raise NotImplementedError("watershed: a %d x %d plane is beyond int32 pixels" % (h, w))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=elevation.device)
+    stats = np.zeros(len(WATERSHED_STATS), dtype=np.int64)
+    _capi.call("pxsom_watershed", elevation.data_ptr(), lde, markers.data_ptr(), ldm, h, w, out.data_ptr(), _ld(out),
+               ws.data_ptr(), wsb, stats.ctypes.data, _capi.stream_ptr())
+    return (out, dict(zip(WATERSHED_STATS, (int(s) for s in stats)))) if return_stats else out
+
+
+def channel_fiber_labels(channel: torch.Tensor, blur=2.0, kernel_size=8, sigmas=FRANGI_SIGMAS, ridge_cutoff: float = 0.1,
+                         sobel_blur: float = 1, thresholds=None, min_fiber_size: int = 15, clip_limit=0.01, beta=0.5,
+                         gamma=15.0):
+    """``segment_fibers`` from the raw channel (a contiguous ``[H, W]`` float64 HBM plane) to its filtered fibre labels, as
+    one chain on the device: :func:`channel_watershed_inputs`, :func:`watershed` of its elevation and markers, the pixels
+    labelled 2 (the reference's ``watershed(...) - 1``) as the mask, :func:`label_components` (4-connected) and
+    :func:`components_select` ("keep", ``min_area=min_fiber_size``; not renumbered).  Returns ``(labels, contrast, ridges,
+    dist, (t0, t1), markers, elevation)``: the int32 labels and the planes the debug files need, all in HBM.  The host sees
+    what the K25 chain and the watershed's rounds read back, never a plane."""
+    contrast, ridges, dist, t, markers, elevation = channel_watershed_inputs(channel, blur, kernel_size, sigmas, ridge_cutoff,
+                                                                             sobel_blur, thresholds, clip_limit, beta, gamma)
+    flooded = watershed(elevation, markers)
+    labels, _, areas = label_components(flooded == 2, connectivity=1)
+    labels = components_select(labels, areas, "keep", min_area=int(min_fiber_size), out=labels)
+    return labels, contrast, ridges, dist, t, markers, elevation

@@ -1147,6 +1147,37 @@ int pxsom_clahe_equalize(const uint16_t *gray_dev, int h, int w, int64_t ld, int
                          double *out_dev, int64_t ld_out, uint16_t *maps_out_dev, uint16_t *raw_out_dev, int64_t ld_raw,
                          void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- fibre segmentation, the marker watershed (K28) ---------------------------------------------------------------------
+ * reference: ark/segmentation/fiber_segmentation.py segment_fibers,
+ *   segmentation = watershed(elevation_map.astype(np.int32), threshed.astype(np.int32)) - 1
+ * pxsom_watershed is skimage 0.19's watershed(image, markers) at its defaults (connectivity 1, no mask, no compactness, no
+ * watershed line) as recalled; tests/watershed_reference.py is the same statement in Python, and parity with skimage itself
+ * is unpinned.  Symbols added under ABI 9, none changed.  The statement: a priority flood over a heap keyed (value, age).
+ * Every pixel with a non-zero marker is pushed in raster order (markers of one value pop in raster order; skimage leaves
+ * that to its heap); a popped pixel gives its label to each still unlabelled 4-neighbour, visited in the order -W, -1, +1,
+ * +W, and pushes it: a pixel is labelled when it is pushed, and the first neighbour popped decides.  Any non-zero marker
+ * value is a label, negative ones included.  A plane without a marker returns all zeros.
+ *
+ * The device computes that result in rounds (csrc/pxsom_watershed.hip states them): per level the frontier claims its
+ * neighbours with atomicMin on a 64-bit key per pixel, basins below the level are taken whole through
+ * pxsom_label_components, and the winners are emitted in key order by an exclusive scan.  The rounds are driven from the
+ * host inside the entry, which therefore SYNCHRONISES the stream once per round (a 40-byte read-back).  Rounds and levels
+ * are each at most h * w; crossing that bound returns PXSOM_ERR_HIP ("internal error") instead of launching again.
+ *   elev_dev     [h, w] int32, row stride lde: the elevation, any int32 values
+ *   markers_dev  [h, w] int32, row stride ldm
+ *   out_dev      [h, w] int32, row stride ldo, every pixel written; must not overlap either input
+ *   workspace    pxsom_watershed_workspace_bytes(h, w) bytes (about 54 per pixel; 0 for refused sizes), 16-byte aligned
+ *   stats_host   NULL, or four int64 on the HOST: rounds, levels visited, rounds that took the basin path, pixels the flood
+ *                labelled (the markers themselves are not counted)
+ * Null or misaligned pointers, h or w < 1, strides < w, out overlapping an input: PXSOM_ERR_INVALID_ARG before any HIP call;
+ * a short or null workspace: PXSOM_ERR_WORKSPACE; a plane beyond what pxsom_label_components takes (h * w > 2^31 - 1):
+ * PXSOM_ERR_UNSUPPORTED.  Integer atomics only, and no label depends on their order: the same input gives the same bits on
+ * every run. */
+size_t pxsom_watershed_workspace_bytes(int h, int w);
+int pxsom_watershed(const int32_t *elev_dev, int64_t lde, const int32_t *markers_dev, int64_t ldm, int h, int w,
+                    int32_t *out_dev, int64_t ldo, void *workspace_dev, size_t workspace_bytes, int64_t *stats_host,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif
