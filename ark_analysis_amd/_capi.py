@@ -170,6 +170,9 @@ SYMBOLS = {
     "pxsom_clahe_equalize": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _f64, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
     "pxsom_watershed_workspace_bytes": (_sz, [_i32, _i32]),
     "pxsom_watershed": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp, _vp]),
+    "pxsom_percentile_f32_listq": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "pxsom_overlay_rgb": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pxsom_colorize": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

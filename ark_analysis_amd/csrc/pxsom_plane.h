@@ -1,5 +1,6 @@
 // pxsom_plane.h -- what the image-plane and cell kernels (K10 - K16) share: dispatch over the PXSOM_SEG_* dtype codes,
-// the grid of a grid-stride launch, the blur taps and borders.  (The key table of K10 / K12 is pxsom_keytable.h.)
+// the grid of a grid-stride launch, the 4-pixel vector and neighbour-lane shuffles of the K10 / K29 tile, the blur taps and
+// borders.  (The key table of K10 / K12 is pxsom_keytable.h.)
 //
 // The device functions and the kernel-argument structs sit in an unnamed namespace, i.e. they are `static`: every unit
 // that includes this header gets its own copy.  That keeps the mangled names of the kernels that take a Taps what they
@@ -81,6 +82,30 @@ __device__ __forceinline__ int64_t xcd_contiguous(int64_t b, int64_t nb)
     constexpr int kXcds = 8;
     const int64_t per = (nb + kXcds - 1) / kXcds;
     return (b % kXcds) * per + b / kXcds;     // may be >= nb: the caller skips those
+}
+
+// ---- a lane's 4 consecutive pixels and its neighbours' (the tile shape of K10 and K29) ----
+template <typename T>
+struct Vec4 {
+    typedef T type __attribute__((ext_vector_type(4)));
+};
+
+template <typename T>
+__device__ __forceinline__ T shfl_up1(T v)
+{
+    if constexpr (sizeof(T) == 8)
+        return (T)__shfl_up((long long)v, 1, 64);
+    else
+        return (T)__shfl_up((int)v, 1, 64);
+}
+
+template <typename T>
+__device__ __forceinline__ T shfl_down1(T v)
+{
+    if constexpr (sizeof(T) == 8)
+        return (T)__shfl_down((long long)v, 1, 64);
+    else
+        return (T)__shfl_down((int)v, 1, 64);
 }
 
 // ---- blur taps and borders ----

@@ -560,6 +560,19 @@ __global__ void q_finish_kernel(const QState *st, int c, double q, double *out, 
         out[col] = __longlong_as_double(0x7ff8000000000000ll);  // NaN, like pandas for an all-zero column
         return;
     }
+    if (arith32 == 2) {  // numpy on a float32 array with a LIST of q: index and fraction in binary64, b - a in binary32, the
+                         // interpolation in binary64 (pxsom_percentile_f32_listq)
+        const double vi = q * (double)(s.m - 1);
+        unsigned long long lo = (unsigned long long)floor(vi);
+        if (lo > s.m - 1) lo = s.m - 1;
+        const unsigned long long hi = lo + 1 > s.m - 1 ? s.m - 1 : lo + 1;
+        const double g = vi - (double)lo;
+        const float a = (float)key_f64(s.prefix);
+        const float b = (hi == lo || s.count_le > hi) ? a : (float)key_f64(s.hi_key);
+        const double diff = (double)(b - a);
+        out[col] = g >= 0.5 ? (double)b - diff * (1.0 - g) : (double)a + diff * g;
+        return;
+    }
     if (arith32) {  // numpy on a float32 array: index, fraction and interpolation in binary32
         const float vi = (float)(s.m - 1) * (float)q;
         unsigned long long lo = (unsigned long long)floorf(vi);
@@ -832,7 +845,7 @@ int quantile_typed(const char *fn, const T *x_dev, int64_t n, int c, int64_t ldx
         for (int col0 = 0; col0 < c; col0 += kQCols)
             hipLaunchKernelGGL(q_hist_kernel<T>, dim3(rgrid), dim3(256), 0, st, x_dev, n, c, ldx, keep_mode, shift, qs, hist, first,
                                col0, std::min(kQCols, c - col0));
-        hipLaunchKernelGGL(q_select_kernel, dim3(c), dim3(64), 0, st, qs, hist, c, shift, q, first, arith32,
+        hipLaunchKernelGGL(q_select_kernel, dim3(c), dim3(64), 0, st, qs, hist, c, shift, q, first, arith32 == 1 ? 1 : 0,
                            (shift == last_shift && last_shift > 0) ? last_shift : 0);
     }
     for (int col0 = 0; col0 < c; col0 += kQCols)
@@ -859,6 +872,24 @@ PXSOM_EXPORT int pxsom_quantile_f32(const float *x_dev, int64_t n, int c, int64_
 {
     return quantile_typed<float>("pxsom_quantile_f32", x_dev, n, c, ldx, q, keep_mode, out_dev, workspace_dev,
                                  workspace_bytes, 1, reinterpret_cast<hipStream_t>(stream));
+}
+
+// np.percentile(x[kept], [q...]) of float32 columns: the select of pxsom_quantile_f32 once per q, finished with the
+// arithmetic numpy uses for a list of q (q_finish_kernel, mode 2).  out_dev [n_q, c].
+PXSOM_EXPORT int pxsom_percentile_f32_listq(const float *x_dev, int64_t n, int c, int64_t ldx, const double *q_host, int n_q,
+                                            int keep_mode, double *out_dev, void *workspace_dev, size_t workspace_bytes,
+                                            void *stream)
+{
+    const char *fn = "pxsom_percentile_f32_listq";
+    if (!q_host || n_q < 1 || !out_dev) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: bad arguments", fn);
+    for (int i = 0; i < n_q; i++)
+        if (!(q_host[i] >= 0.0 && q_host[i] <= 1.0)) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: q[%d] outside [0, 1]", fn, i);
+    for (int i = 0; i < n_q; i++) {
+        const int rc = quantile_typed<float>(fn, x_dev, n, c, ldx, q_host[i], keep_mode, out_dev + (int64_t)i * c, workspace_dev,
+                                             workspace_bytes, 2, reinterpret_cast<hipStream_t>(stream));
+        if (rc != PXSOM_OK) return rc;
+    }
+    return PXSOM_OK;
 }
 
 // out[i] = sum_j img[i, j] / norm[j] in float32, added up the way numpy adds a contiguous float32 axis of at

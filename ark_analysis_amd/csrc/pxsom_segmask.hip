@@ -25,29 +25,6 @@ constexpr int kRowsPerWave = 4;
 constexpr int kWaves = 4;
 constexpr int kBlockRows = kRowsPerWave * kWaves;
 
-template <typename T>
-struct Vec4 {
-    typedef T type __attribute__((ext_vector_type(4)));
-};
-
-template <typename T>
-__device__ __forceinline__ T shfl_up1(T v)
-{
-    if constexpr (sizeof(T) == 8)
-        return (T)__shfl_up((long long)v, 1, 64);
-    else
-        return (T)__shfl_up((int)v, 1, 64);
-}
-
-template <typename T>
-__device__ __forceinline__ T shfl_down1(T v)
-{
-    if constexpr (sizeof(T) == 8)
-        return (T)__shfl_down((long long)v, 1, 64);
-    else
-        return (T)__shfl_down((int)v, 1, 64);
-}
-
 // 4 labels of row r from column c0: one wide load when the 4 lie inside the row and the rows are aligned, else element
 // loads with the column clamped to w - 1 (the clamp is scipy's reflect at distance 1: the right neighbour of the last
 // column is the column itself)

@@ -105,34 +105,47 @@ def read_image(path, out=None) -> np.ndarray:
 _SAMPLE_KINDS = {1: "u", 2: "i", 3: "f"}
 
 
+def _tiff_header(f, path):
+    """``(byte order, offset of the first image directory)`` of an open TIFF; the offset is None for a BigTIFF."""
+    import struct
+    head = f.read(8)
+    if len(head) < 8 or head[:2] not in (b"II", b"MM"):
+        raise ValueError("%s is not a TIFF file" % path)
+    bo = "<" if head[:2] == b"II" else ">"
+    magic, first = struct.unpack(bo + "HI", head[2:8])
+    return bo, (first if magic == 42 else None)
+
+
+def _read_directory(f, bo, offset):
+    """``({tag: values}, offset of the next directory or 0)`` of the image directory at ``offset`` of a classic TIFF."""
+    import struct
+    f.seek(offset)
+    (count,) = struct.unpack(bo + "H", f.read(2))
+    raw = f.read(12 * count + 4)
+    sizes = {1: ("B", 1), 2: ("s", 1), 3: ("H", 2), 4: ("I", 4), 16: ("Q", 8)}
+    tags = {}
+    for i in range(count):
+        tag, kind, n = struct.unpack(bo + "HHI", raw[12 * i:12 * i + 8])
+        if kind not in sizes:
+            continue
+        code, size = sizes[kind]
+        body = raw[12 * i + 8:12 * i + 12]
+        if n * size > 4:
+            (where,) = struct.unpack(bo + "I", body)
+            f.seek(where)
+            body = f.read(n * size)
+        tags[tag] = body[:n] if code == "s" else struct.unpack(bo + code * n, body[:n * size])
+    (next_ifd,) = struct.unpack(bo + "I", raw[12 * count:12 * count + 4])
+    return tags, next_ifd
+
+
 def _tiff_directory(path):
     """``(byte order, {tag: values})`` of the first image directory of a classic TIFF, plus whether more pages follow."""
-    import struct
     with open(path, "rb") as f:
-        head = f.read(8)
-        if len(head) < 8 or head[:2] not in (b"II", b"MM"):
-            raise ValueError("%s is not a TIFF file" % path)
-        bo = "<" if head[:2] == b"II" else ">"
-        magic, first = struct.unpack(bo + "HI", head[2:8])
-        if magic != 42:
+        bo, first = _tiff_header(f, path)
+        if first is None:
             return bo, None, False          # BigTIFF: left to Pillow
-        f.seek(first)
-        (count,) = struct.unpack(bo + "H", f.read(2))
-        raw = f.read(12 * count + 4)
-        sizes = {1: ("B", 1), 2: ("s", 1), 3: ("H", 2), 4: ("I", 4), 16: ("Q", 8)}
-        tags = {}
-        for i in range(count):
-            tag, kind, n = struct.unpack(bo + "HHI", raw[12 * i:12 * i + 8])
-            if kind not in sizes:
-                continue
-            code, size = sizes[kind]
-            body = raw[12 * i + 8:12 * i + 12]
-            if n * size > 4:
-                (offset,) = struct.unpack(bo + "I", body)
-                f.seek(offset)
-                body = f.read(n * size)
-            tags[tag] = body[:n] if code == "s" else struct.unpack(bo + code * n, body[:n * size])
-        (next_ifd,) = struct.unpack(bo + "I", raw[12 * count:12 * count + 4])
+        tags, next_ifd = _read_directory(f, bo, first)
     return bo, tags, next_ifd != 0
 
 
@@ -296,3 +309,123 @@ def write_image(path, image: np.ndarray) -> None:
     with open(path, "wb") as f:
         f.write(b"II*\0" + struct.pack("<I", 8) + directory + struct.pack("<I", 0))
         f.write(memoryview(data).cast("B"))
+
+
+# ---- multi-page stacks and colour images (K29: the Mesmer input, the overlays, the coloured masks) -------------------
+_STACK_DTYPES = ("uint8", "uint16", "int16", "int32", "uint32", "float32")
+
+
+def _directory_bytes(entries, offset, next_ifd):
+    """An image directory placed at ``offset``: ``entries`` are ``(tag, kind, values)`` with kind 3 (SHORT) or 4 (LONG);
+    values longer than four bytes lie right behind the directory."""
+    import struct
+    after = offset + 2 + 12 * len(entries) + 4
+    body, extra = b"", b""
+    for tag, kind, values in entries:
+        raw = struct.pack("<%d%s" % (len(values), "H" if kind == 3 else "I"), *values)
+        if len(raw) <= 4:
+            field = raw.ljust(4, b"\0")
+        else:
+            field = struct.pack("<I", after + len(extra))
+            extra += raw + (b"\0" if len(raw) % 2 else b"")
+        body += struct.pack("<HHI", tag, kind, len(values)) + field
+    return struct.pack("<H", len(entries)) + body + struct.pack("<I", next_ifd) + extra
+
+
+def _page_entries(height, width, bits, sample_format, samples, strip_offset, nbytes):
+    short, long_ = 3, 4
+    entries = [(256, long_, (width,)), (257, long_, (height,)), (258, short, (bits,) * samples), (259, short, (1,)),
+               (262, short, (2 if samples >= 3 else 1,)), (273, long_, (strip_offset,)), (277, short, (samples,)),
+               (278, long_, (height,)), (279, long_, (nbytes,))]
+    if samples == 4:
+        entries.append((338, short, (2,)))          # ExtraSamples: unassociated alpha
+    entries.append((339, short, (sample_format,) * samples))
+    return entries
+
+
+def _write_pages(path, pages, samples):
+    """``pages``: C-contiguous little-endian arrays of one shape and dtype, each written as directory, then its one strip."""
+    dtype = pages[0].dtype
+    height, width = pages[0].shape[:2]
+    bits, fmt = dtype.itemsize * 8, _SAMPLE_FORMATS[dtype.kind]
+    nbytes = pages[0].nbytes
+    dir_len = len(_directory_bytes(_page_entries(height, width, bits, fmt, samples, 0, nbytes), 0, 0))
+    stride = dir_len + nbytes + (nbytes % 2)        # directories start on even offsets
+    if 8 + stride * len(pages) >= 1 << 32:
+        raise ValueError("image too large for a classic TIFF")
+    with open(path, "wb") as f:
+        f.write(b"II*\0\x08\0\0\0")
+        for i, page in enumerate(pages):
+            offset = 8 + i * stride
+            entries = _page_entries(height, width, bits, fmt, samples, offset + dir_len, nbytes)
+            f.write(_directory_bytes(entries, offset, offset + stride if i + 1 < len(pages) else 0))
+            f.write(memoryview(page).cast("B"))
+            if nbytes % 2:
+                f.write(b"\0")
+
+
+def write_stack(path, pages: np.ndarray) -> None:
+    """A ``[P, H, W]`` uint8 / uint16 / int16 / int32 / uint32 / float32 array as a classic multi-page TIFF: little-endian,
+    uncompressed, one strip per page, every page of the one shape and dtype -- the channels-first file
+    ``generate_deepcell_input`` hands to Mesmer.  :func:`read_stack` reads it back unchanged."""
+    pages = np.asarray(pages)
+    if pages.ndim != 3 or pages.shape[0] < 1 or pages.size == 0 or pages.dtype.name not in _STACK_DTYPES:
+        raise ValueError("write_stack takes a non-empty [P, H, W] uint8, uint16, int16, int32, uint32 or float32 array, "
+                         "got %s %s" % (pages.dtype, pages.shape))
+    data = np.ascontiguousarray(pages, dtype=pages.dtype.newbyteorder("<"))
+    _write_pages(path, [data[i] for i in range(data.shape[0])], 1)
+
+
+def write_rgb(path, image: np.ndarray) -> None:
+    """A uint8 ``[H, W, 3]`` (RGB) or ``[H, W, 4]`` (RGB and unassociated alpha) array as a baseline TIFF: uncompressed,
+    one strip, samples interleaved -- what the overlays and the coloured masks are saved as."""
+    image = np.asarray(image)
+    if image.ndim != 3 or image.shape[2] not in (3, 4) or image.dtype != np.uint8 or image.size == 0:
+        raise ValueError("write_rgb takes a non-empty uint8 [H, W, 3] or [H, W, 4] array, got %s %s" % (image.dtype, image.shape))
+    _write_pages(path, [np.ascontiguousarray(image)], image.shape[2])
+
+
+def read_stack(path) -> np.ndarray:
+    """Every page of a TIFF as ``[P, H, W]`` in the file's own dtype (a single-page file gives ``P = 1``).  Uncompressed
+    pages of one sample per pixel are read here strip by strip; a file holding anything else goes through Pillow page by
+    page.  The pages must have one shape and dtype."""
+    pages = None
+    with open(path, "rb") as f:
+        bo, offset = _tiff_header(f, path)
+        if offset is not None:
+            pages = []
+            seen = set()
+            while offset and pages is not None:
+                if offset in seen:
+                    raise ValueError("%s: its image directories form a loop" % path)
+                seen.add(offset)
+                tags, offset = _read_directory(f, bo, offset)
+                width, height = tags.get(256, (0,))[0], tags.get(257, (0,))[0]
+                bits = tags.get(258, (1,))[0]
+                kind = _SAMPLE_KINDS.get(tags.get(339, (1,))[0])
+                plain = (tags.get(277, (1,))[0] == 1 and 273 in tags and 279 in tags and kind is not None
+                         and bits in (8, 16, 32, 64) and tags.get(259, (1,))[0] == 1 and not (kind == "f" and bits == 8)
+                         and width > 0 and height > 0)
+                if not plain:
+                    pages = None
+                    break
+                chunks = []
+                for where, nbytes in zip(tags[273], tags[279]):
+                    f.seek(where)
+                    chunks.append(f.read(nbytes))
+                dtype = np.dtype(bo + kind + str(bits // 8))
+                flat = np.frombuffer(b"".join(chunks), dtype=dtype)
+                if flat.size < width * height:
+                    pages = None
+                    break
+                pages.append(flat[:width * height].reshape(height, width).astype(dtype.newbyteorder("=")))
+    if pages is None:
+        from PIL import Image
+        with Image.open(path) as im:
+            pages = []
+            for i in range(getattr(im, "n_frames", 1)):
+                im.seek(i)
+                pages.append(np.array(im))
+    if any(p.shape != pages[0].shape or p.dtype != pages[0].dtype for p in pages):
+        raise ValueError("%s: its pages differ in shape or dtype" % path)
+    return np.stack(pages, axis=0)

@@ -8,14 +8,17 @@ plane.  The reference builds two full-image masks per cell instead.  skimage's `
 documented behaviour on an integer array (sizes by ``bincount``, no connected components); its "only one label was
 provided" warning is not reproduced.
 
-``transform_expression_matrix`` and ``save_segmentation_labels`` are not mirrored: the first takes and returns an
-xarray (generate_cell_table applies both transforms itself), the second needs ``find_boundaries`` and the plotting
-module."""
+``save_segmentation_labels`` writes the border plane and the channel overlays of every FOV through the one-pass overlay
+kernel (``utils/plot_utils.py``).
+
+``transform_expression_matrix`` is not mirrored: it takes and returns an xarray (generate_cell_table applies both
+transforms itself)."""
 import os
 
 import numpy as np
 import pandas as pd
 
+from .. import image_io
 from ..host_utils import remove_file_extensions
 
 INT32_MAX = 2 ** 31 - 1
@@ -101,3 +104,25 @@ def concatenate_csv(base_dir, csv_files, column_name="fov", column_values=None):
         temp_data[column_name] = column_values[idx]
         combined_data = temp_data if idx == 0 else pd.concat((combined_data, temp_data), axis=0, ignore_index=True)
     combined_data.to_csv(os.path.join(base_dir, "combined_data.csv"), index=False)
+
+
+def save_segmentation_labels(segmentation_dir, data_dir, output_dir, fovs, channels=None):
+    """For every FOV of ``fovs``: the inner borders of ``<segmentation_dir>/<fov>_whole_cell.tiff`` as
+    ``<output_dir>/<fov>_segmentation_borders.tiff`` (uint8, 0 / 255) and, with ``channels`` (of ``nuclear_channel``,
+    ``membrane_channel``: the pages of ``<data_dir>/<fov>.tiff``), their overlay under those borders as
+    ``<output_dir>/<fov>_<chan>_..._overlay.tiff`` (uint8 RGB).  Both images of a FOV are computed before either file is
+    written, so a refusal (``plot_utils.create_overlay``) leaves no file of that FOV behind."""
+    from ..utils import plot_utils
+    for fov in fovs:
+        channel_overlay = None
+        if channels is None:
+            labels = np.squeeze(image_io.read_tiff_shaped(os.path.join(segmentation_dir, fov + "_whole_cell.tiff")))
+            contour_mask = plot_utils.segmentation_borders(labels)
+        else:
+            chans = np.array(channels)      # (an array, so that chans.astype("str") names the file as the reference does)
+            channel_overlay, contour_mask = plot_utils._create_overlay(fov, segmentation_dir, data_dir, chans, "whole_cell",
+                                                                       None, True)
+        image_io.write_image(os.path.join(output_dir, f"{fov}_segmentation_borders.tiff"), contour_mask)
+        if channel_overlay is not None:
+            save_path = "_".join([f"{fov}", *chans.astype("str"), "overlay.tiff"])
+            image_io.write_rgb(os.path.join(output_dir, save_path), channel_overlay)

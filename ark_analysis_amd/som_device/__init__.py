@@ -31,6 +31,8 @@ from .planes import FRANGI_SIGMAS, GRADIENT_TOO_SMALL, frangi, frangi_arguments,
 from .planes import (CLAHE_GREY_LEVELS, CLAHE_NBINS, channel_watershed_inputs, clahe_arguments, contrast_adjust,
                      equalize_adapthist)
 from .planes import WATERSHED_STATS, channel_fiber_labels, watershed
+from .overlays import (COLORIZE_BAD_INDEX, COLORIZE_MASK_DTYPES, OVERLAY_CLIP, OVERLAY_RESCALE, OVERLAY_ZERO, colorize,
+                       overlay_compose, overlay_ranges, overlay_rgb, percentiles_positive)
 from .cells import (CELLQUANT_FORCE_SEARCH, CELLQUANT_IMAGE_DTYPES, CELLQUANT_MODES, CELLQUANT_NUC_CAPACITY,
                     CONCAVITY_DEFAULTS, NUCSPLIT_FORCE_SEARCH, REGION_FORCE_SEARCH, REGION_MAX_SIDE, cell_quantify,
                     choose_splits, label_keys, nuclear_overlaps, region_euler, region_moments, region_props,

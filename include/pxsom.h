@@ -1178,6 +1178,51 @@ int pxsom_watershed(const int32_t *elev_dev, int64_t lde, const int32_t *markers
                     int32_t *out_dev, int64_t ldo, void *workspace_dev, size_t workspace_bytes, int64_t *stats_host,
                     void *stream);
 
+/* ---- cell overlays, Mesmer inputs and coloured masks (K29) --------------------------------------------------------------
+ * reference: ark/utils/plot_utils.py create_overlay (:567-603) and save_colored_masks (:876), ark/segmentation/
+ * segmentation_utils.py save_segmentation_labels (:217-219).  Symbols added under ABI 9, none changed.
+ * tests/overlay_reference.py is the same statement in numpy; skimage's rescale_intensity is taken as recalled (0.19).
+ *
+ * pxsom_percentile_f32_listq: np.percentile(x[kept], [q...]) of float32 columns with the arithmetic numpy uses for a LIST
+ * of q on a float32 array, which is not pxsom_quantile_f32's (a scalar q): the virtual index q (m - 1), its floor and the
+ * fraction g are binary64, b - a is binary32, and the interpolation a + d g (g < 0.5) or b - d (1 - g) is binary64.
+ * q_host [n_q] holds the quantiles q / 100 in [0, 1]; out_dev [n_q, c] binary64, NaN for a column without a kept value.
+ * Same radix select, keep modes and workspace as pxsom_quantile_f32 (pxsom_quantile_workspace_bytes(n, c)).
+ *
+ * pxsom_overlay_rgb: one pass over contiguous [h, w] planes.  Per pixel, first the border test of each label plane,
+ * find_boundaries(labels, connectivity=1, mode="inner") as pxsom_segmask states it: an in-image 4-neighbour holds another
+ * label (compared in the label dtype; a neighbour outside the image counts as equal) and the pixel's own label is not 0.
+ * Then per output byte j (0 red, 1 green, 2 blue), from plane j of plane_dtype (PXSOM_SEG_U8, _I16, _U16, _I32 or _F32):
+ *   PXSOM_OVERLAY_ZERO     0 (an absent channel, or one whose maximum is 0); the plane may be NULL
+ *   PXSOM_OVERLAY_RESCALE  y = clip(x, lo, hi); y = (y - lo) / (hi - lo) * 255.0 + 0.0; the C cast to uint8   (lo < hi)
+ *   PXSOM_OVERLAY_CLIP     clip(clip(x, lo, hi), 0, 255) cast to uint8                                         (lo == hi)
+ * with numpy 2's arithmetic: for a float32 plane every operation is binary32 and lo, hi, hi - lo (formed in binary64) and
+ * 255.0 are each rounded to binary32 first; for an integer plane everything is binary64.  One rounding per operation (no
+ * contraction), correctly rounded division.  A NaN pixel gives an unspecified byte.  Then a border pixel of seg sets the
+ * three bytes to 255, and after that a border pixel of alt sets red 255, green and blue 0.
+ *   r_dev, g_dev, b_dev   the planes of the three output bytes, each NULL under PXSOM_OVERLAY_ZERO
+ *   modes_host [3], ranges_host [3][2] = (lo, hi) per output byte, on the HOST; ignored without rgb_dev
+ *   seg_dev    [h, w] of seg_dtype (PXSOM_SEG_U8 .. PXSOM_SEG_I64);  alt_dev NULL or [h, w] of alt_dtype
+ *   rgb_dev    NULL or uint8 [h, w, 3];  borders_dev NULL or uint8 [h, w], 255 on a border pixel of seg and 0 elsewhere
+ * Sizes < 1, a null seg, no output at all, unknown dtype or mode, a mode without its plane, a range that is not finite or
+ * does not fit the mode, an output overlapping a label plane: PXSOM_ERR_INVALID_ARG before any HIP call.
+ *
+ * pxsom_colorize: out[p, :] = table[mask[p], :] for a contiguous [h, w] mask (PXSOM_SEG_U8, _I16, _U16 or _I32), a uint8
+ * table [n_rows, n_cols] with n_cols 3 or 4 and a uint8 output [h, w, n_cols].  status_dev (one int32, zeroed by the call)
+ * gets PXSOM_COLORIZE_BAD_INDEX when an index lies outside [0, n_rows); such a pixel is written as zeros.  Negative indices
+ * are refused although numpy would wrap them (as pxsom_cluster_mask refuses them). */
+#define PXSOM_OVERLAY_ZERO 0
+#define PXSOM_OVERLAY_RESCALE 1
+#define PXSOM_OVERLAY_CLIP 2
+#define PXSOM_COLORIZE_BAD_INDEX 1
+int pxsom_percentile_f32_listq(const float *x_dev, int64_t n, int c, int64_t ldx, const double *q_host, int n_q,
+                               int keep_mode, double *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int pxsom_overlay_rgb(const void *r_dev, const void *g_dev, const void *b_dev, int plane_dtype, const int32_t *modes_host,
+                      const double *ranges_host, const void *seg_dev, int seg_dtype, const void *alt_dev, int alt_dtype,
+                      int h, int w, uint8_t *rgb_dev, uint8_t *borders_dev, void *stream);
+int pxsom_colorize(const void *mask_dev, int mask_dtype, int h, int w, const uint8_t *table_dev, int n_rows, int n_cols,
+                   uint8_t *out_dev, int32_t *status_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
