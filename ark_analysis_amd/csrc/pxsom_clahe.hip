@@ -29,6 +29,8 @@
 #include <cstdint>
 
 #include "pxsom_common.h"
+#include "pxsom_plane.h"
+#include "pxsom_wave.h"
 
 namespace {
 
@@ -67,13 +69,6 @@ __global__ __launch_bounds__(256) void quantize_kernel(const double *__restrict_
     t = rint(t);                                               // half to even
     const int q = t >= 0.0 ? (t <= kGreyMax ? (int)t : (int)kGreyMax) : 0;     // (a NaN pixel: 0)
     gray[(int64_t)y * ldg + x] = (uint16_t)q;
-}
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 __device__ __forceinline__ int popc(unsigned long long m) { return __popcll(m); }
@@ -125,7 +120,7 @@ __global__ __launch_bounds__(256) void tile_maps_kernel(const uint16_t *__restri
             part += hv[q] - cl;
             hv[q] = cl;
         }
-    long long n_excess = wave_sum(part);
+    long long n_excess = pxsom::wave_sum(part);
     const long long bin_incr = n_excess / kBins;
     const long long upper = (long long)cl - bin_incr;
     part = 0;
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(256) void tile_maps_kernel(const uint16_t *__restri
             hv[q] += (int)bin_incr;
             part++;
         }
-    n_excess -= wave_sum(part) * bin_incr;
+    n_excess -= pxsom::wave_sum(part) * bin_incr;
     part = 0;
 #pragma unroll
     for (int q = 0; q < 4; q++)                                // on the updated counts, as the statement has it
@@ -143,7 +138,7 @@ __global__ __launch_bounds__(256) void tile_maps_kernel(const uint16_t *__restri
             part += hv[q] - cl;
             hv[q] = cl;
         }
-    n_excess += wave_sum(part);
+    n_excess += pxsom::wave_sum(part);
     bool spent = false;
     while (n_excess > 0 && !spent) {
         const long long prev = n_excess;
@@ -262,14 +257,14 @@ __global__ __launch_bounds__(256) void rescale_kernel(const uint16_t *__restrict
 bool is_finite(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }
 
 struct Span {
-    uintptr_t lo, hi;
+    const void *p;
+    size_t bytes;
     const char *name;
 };
 
 Span plane_span(const void *p, int h, int w, int64_t ld, size_t elem, const char *name)
 {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return Span{lo, lo + ((uintptr_t)(h - 1) * (uintptr_t)ld + (uintptr_t)w) * elem, name};
+    return Span{p, pxsom::plane_span_bytes(h, w, ld, elem), name};
 }
 
 // the first two of n spans that share a byte, or -1
@@ -277,7 +272,7 @@ int first_overlap(const Span *s, int n, int *other)
 {
     for (int i = 0; i < n; i++)
         for (int j = i + 1; j < n; j++)
-            if (s[i].lo < s[j].hi && s[j].lo < s[i].hi) {
+            if (pxsom::spans_overlap(s[i].p, s[i].bytes, s[j].p, s[j].bytes)) {
                 *other = j;
                 return i;
             }
@@ -382,13 +377,10 @@ PXSOM_EXPORT int pxsom_clahe_equalize(const uint16_t *gray_dev, int h, int w, in
     const size_t need = pxsom_clahe_workspace_bytes(h, w, k);
     if (workspace_bytes < need) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
     {
-        const uintptr_t ws = reinterpret_cast<uintptr_t>(workspace_dev);
-        Span s[5] = {plane_span(gray_dev, h, w, ld, 2, "gray"), plane_span(out_dev, h, w, ld_out, 8, "out"), Span{ws, ws + need, "workspace"}};
+        Span s[5] = {plane_span(gray_dev, h, w, ld, 2, "gray"), plane_span(out_dev, h, w, ld_out, 8, "out"),
+                     Span{workspace_dev, need, "workspace"}};
         int n = 3;
-        if (maps_out_dev) {
-            const uintptr_t m = reinterpret_cast<uintptr_t>(maps_out_dev);
-            s[n++] = Span{m, m + maps_bytes(h, w, k), "maps_out"};
-        }
+        if (maps_out_dev) s[n++] = Span{maps_out_dev, maps_bytes(h, w, k), "maps_out"};
         if (raw_out_dev) s[n++] = plane_span(raw_out_dev, h, w, ld_raw, 2, "raw_out");
         int other;
         const int one = first_overlap(s, n, &other);

@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "pxsom_common.h"
+#include "pxsom_plane.h"
 
 namespace {
 
@@ -86,13 +87,9 @@ __global__ __launch_bounds__(256) void frangi_scale_kernel(const double *__restr
     const double hrr = s2 * gradient(g0_up, g0_down, ey.inner);
     const double hrc = s2 * gradient(g0_left, g0_right, ex.inner);
     const double hcc = s2 * gradient(g1_left, g1_right, ex.inner);
-    // the eigenvalues, the larger magnitude first; a tie or a NaN takes K22's side
-    const double d = hrr - hcc;
-    const double r = __dsqrt_rn(d * d + 4.0 * (hrc * hrc));
-    const double t = hrr + hcc;
-    const double e_hi = (t + r) / 2.0, e_lo = (t - r) / 2.0;
-    const bool lo_big = fabs(e_lo) >= fabs(e_hi);
-    const double big = lo_big ? e_lo : e_hi, small = lo_big ? e_hi : e_lo;
+    // the eigenvalues, the larger magnitude first, by the rule K22 uses
+    double big, small;
+    hessian_eigenvalues(hrr, hrc, hcc, big, small);
     double den = fabs(big);
     if (den == 0.0) den = 1e-10;
     const double q = small / den;
@@ -124,9 +121,8 @@ PXSOM_EXPORT int pxsom_frangi_scale(const double *g_dev, int64_t ldg, int h, int
     if (!positive_finite(s2) || !positive_finite(bsq) || !positive_finite(gsq))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: s2=%g, bsq=%g, gsq=%g must be finite and > 0", fn, s2, bsq, gsq);
     {   // out must not share a byte with g: every pixel of g is read by its neighbours
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(g_dev), p1 = p0 + ((uintptr_t)(h - 1) * (uintptr_t)ldg + (uintptr_t)w) * 8;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev), o1 = o0 + ((uintptr_t)(h - 1) * (uintptr_t)ldo + (uintptr_t)w) * 8;
-        if (o0 < p1 && p0 < o1) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps g", fn);
+        if (pxsom::spans_overlap(out_dev, pxsom::plane_span_bytes(h, w, ldo, 8), g_dev, pxsom::plane_span_bytes(h, w, ldg, 8)))
+            return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps g", fn);
     }
     if ((int64_t)h * w > 0x7fffffffLL) return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "%s: %d x %d pixels are beyond int32", fn, h, w);
     if ((h + 3) / 4 > 65535) return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "%s: h=%d > %d", fn, h, 4 * 65535);

@@ -277,16 +277,12 @@ PXSOM_EXPORT int pxsom_sobel_magnitude(const double *plane_dev, int h, int w, in
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: row strides %lld / %lld < w=%d", fn, (long long)ldo, (long long)ldi, w);
     if ((reinterpret_cast<uintptr_t>(out_dev) & 7) || (reinterpret_cast<uintptr_t>(out_i32_dev) & 3))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: an output is misaligned", fn);
-    if (out_dev) {   // the magnitude must not share a byte with the plane: every pixel is read by its neighbours
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(plane_dev), p1 = p0 + ((uintptr_t)(h - 1) * (uintptr_t)ld + (uintptr_t)w) * 8;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev), o1 = o0 + ((uintptr_t)(h - 1) * (uintptr_t)ldo + (uintptr_t)w) * 8;
-        if (o0 < p1 && p0 < o1) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps the plane", fn);
-    }
-    if (out_i32_dev) {
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(plane_dev), p1 = p0 + ((uintptr_t)(h - 1) * (uintptr_t)ld + (uintptr_t)w) * 8;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_i32_dev), o1 = o0 + ((uintptr_t)(h - 1) * (uintptr_t)ldi + (uintptr_t)w) * 4;
-        if (o0 < p1 && p0 < o1) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: the int32 output overlaps the plane", fn);
-    }
+    // neither output may share a byte with the plane: every pixel is read by its neighbours
+    const size_t plane_bytes = pxsom::plane_span_bytes(h, w, ld, 8);
+    if (pxsom::spans_overlap(out_dev, pxsom::plane_span_bytes(h, w, ldo, 8), plane_dev, plane_bytes))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps the plane", fn);
+    if (pxsom::spans_overlap(out_i32_dev, pxsom::plane_span_bytes(h, w, ldi, 4), plane_dev, plane_bytes))
+        return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: the int32 output overlaps the plane", fn);
     if (const int rc = plane_size_check(fn, h, w)) return rc;
     if ((h + 3) / 4 > 65535) return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "%s: h=%d > %d", fn, h, 4 * 65535);
     hipLaunchKernelGGL(sobel_magnitude_kernel, dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)), dim3(64, 4), 0,

@@ -16,13 +16,10 @@
 //   4. emit_pairs_kernel    writes the occupied slots as rows and the count
 // Integer atomics only: the same input gives the same bytes on every run.
 #include "pxsom_common.h"
+#include "pxsom_pairtable.h"
 #include "pxsom_plane.h"
 
 namespace {
-
-constexpr unsigned long long kEmpty = ~0ull;
-constexpr int64_t kMaxPairCapacity = int64_t(1) << 27;     // 2^28 slots of 12 bytes: 3 GiB of workspace
-constexpr int kRunSpan = 16 * 256;                         // pixels per workgroup of the two run passes
 
 // the pair of pixel e as a table key, 0 when either label is 0 or outside 1 .. n
 __device__ __forceinline__ unsigned long long pair_key(const int32_t *__restrict__ a, int64_t lda, const int32_t *__restrict__ b,
@@ -60,16 +57,6 @@ __global__ __launch_bounds__(256) void count_runs_kernel(const int32_t *__restri
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(runs, mine);
 }
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long k)
-{
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
-
 __global__ __launch_bounds__(256) void insert_runs_kernel(const int32_t *__restrict__ a, int64_t lda, const int32_t *__restrict__ b,
                                                           int64_t ldb, int w, int64_t total, int32_t n_a, int32_t n_b,
                                                           const int32_t *__restrict__ runs, int64_t capacity,
@@ -89,16 +76,7 @@ __global__ __launch_bounds__(256) void insert_runs_kernel(const int32_t *__restr
         if (!begins) continue;
         const unsigned long long above = lane == 63 ? 0ull : stops >> (lane + 1);
         const int run = above ? __ffsll((long long)above) : 64 - lane;
-        int64_t slot = (int64_t)(mix64(key) & (unsigned long long)(slots - 1));
-        for (int64_t probe = 0; probe < slots; probe++) {  // (ends long before: the table is at most half full)
-            const unsigned long long old = atomicCAS(keys + slot, kEmpty, key);
-            if (old == kEmpty) atomicAdd(n_pairs, 1);
-            if (old == kEmpty || old == key) {
-                atomicAdd(counts + slot, run);
-                break;
-            }
-            slot = (slot + 1) & (slots - 1);
-        }
+        table_add(keys, counts, slots, key, run, n_pairs);
     }
 }
 
@@ -156,21 +134,12 @@ __global__ __launch_bounds__(256) void merge_apply_kernel(const int32_t *__restr
     }
 }
 
-// slots of the table for `capacity` pairs: a power of two, at least twice the capacity
-inline int64_t pair_slots(int64_t capacity)
-{
-    int64_t s = 64;
-    while (s < 2 * capacity) s <<= 1;
-    return s;
-}
-
 }  // namespace
 
 PXSOM_EXPORT size_t pxsom_pair_overlaps_workspace_bytes(int64_t capacity)
 {
     if (capacity < 1 || capacity > kMaxPairCapacity) return 0;
-    const int64_t slots = pair_slots(capacity);
-    return pxsom::align_up((size_t)slots * sizeof(unsigned long long), 256) + pxsom::align_up((size_t)slots * sizeof(int32_t), 256);
+    return pair_table_bytes(capacity);
 }
 
 PXSOM_EXPORT int pxsom_pair_overlaps(const int32_t *a_dev, int64_t lda, const int32_t *b_dev, int64_t ldb, int h, int w,
@@ -204,8 +173,7 @@ PXSOM_EXPORT int pxsom_pair_overlaps(const int32_t *a_dev, int64_t lda, const in
     if (!count_only) {
         const int64_t slots = pair_slots(capacity);
         unsigned long long *keys = static_cast<unsigned long long *>(workspace_dev);
-        int32_t *counts = reinterpret_cast<int32_t *>(static_cast<char *>(workspace_dev) +
-                                                      pxsom::align_up((size_t)slots * sizeof(unsigned long long), 256));
+        int32_t *counts = pair_table_counts(keys, slots);
         PXSOM_HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)slots * sizeof(unsigned long long), st));    // every slot kEmpty
         PXSOM_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)slots * sizeof(int32_t), st));
         hipLaunchKernelGGL(insert_runs_kernel, dim3(spans), dim3(256), 0, st, a_dev, lda, b_dev, ldb, w, total, n_a, n_b,

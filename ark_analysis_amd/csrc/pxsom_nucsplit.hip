@@ -324,7 +324,7 @@ PXSOM_EXPORT int pxsom_nuclear_overlaps(const void *cell_dev, int cell_dtype, in
         const int64_t slots = pair_slots(capacity);
         unsigned long long *top = reinterpret_cast<unsigned long long *>(ws + L.top);
         unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + L.table);
-        int32_t *counts = reinterpret_cast<int32_t *>(ws + L.table + pxsom::align_up((size_t)slots * sizeof(unsigned long long), 256));
+        int32_t *counts = pair_table_counts(keys, slots);
         unsigned long long *area = reinterpret_cast<unsigned long long *>(area_dev);
         PXSOM_HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)slots * sizeof(unsigned long long), st));    // every slot kEmpty
         PXSOM_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)slots * sizeof(int32_t), st));

@@ -7,13 +7,14 @@
 //   pxsom_colorize      the gather of save_colored_masks, (mc_colors[mask] * 255.999).astype(uint8), over a table the host
 //                       has converted once
 //
-// The overlay kernel has K10's shape (pxsom_segmask.hip): a block is 4 waves, a wave owns 256 columns x 4 rows, a lane 4
-// consecutive pixels of each row.  The label rows row0 - 1 .. row0 + 4 are loaded in one sweep (the halo rows are the
-// neighbouring wave's own rows, served by L1 / L2), the left / right neighbour comes from the adjacent lane by a shuffle and
-// only lanes 0 and 63 load one extra element per row.  Labels are compared as raw bits of their width (1, 2, 4 or 8 bytes):
-// equality and "non-zero" do not depend on the sign, so six label dtypes are four instantiations.  A lane's 4 RGB pixels are
-// 12 bytes: three 32-bit words stored together when the row's first byte is 4-byte aligned (always when w % 4 == 0), else
-// byte stores, as at a ragged right edge.  The border plane is one 32-bit word per lane and row under the same rule.
+// The overlay kernel runs on the tile K10 uses (pxsom_plane.h; pxsom_segmask.hip): a block is 4 waves, a wave owns 256
+// columns x 4 rows, a lane 4 consecutive pixels of each row.  load_halo_tile loads the label rows row0 - 1 .. row0 + 4 in one
+// sweep (the halo rows are the neighbouring wave's own rows, served by L1 / L2), the left / right neighbour comes from the
+// adjacent lane by a shuffle and only lanes 0 and 63 load one extra element per row.  Labels are compared as raw bits of
+// their width (1, 2, 4 or 8 bytes): equality and "non-zero" do not depend on the sign, so six label dtypes are four
+// instantiations.  A lane's 4 RGB pixels are 12 bytes: three 32-bit words stored together when the row's first byte is 4-byte
+// aligned (always when w % 4 == 0), else byte stores, as at a ragged right edge.  The border plane is one 32-bit word per
+// lane and row under the same rule.
 //
 // The arithmetic of the rescale is numpy 2's: binary32 throughout for a float32 plane, binary64 for an integer plane, one
 // rounding per operation.  No contraction in this file.
@@ -25,32 +26,6 @@
 
 namespace {
 
-constexpr int kWaveCols = 256;       // 64 lanes x 4 pixels
-constexpr int kRowsPerWave = 4;
-constexpr int kWaves = 4;
-constexpr int kBlockRows = kRowsPerWave * kWaves;
-
-// 4 elements of row r of a contiguous [h, w] plane from column c0: one wide load when the 4 lie inside the row and the
-// rows are aligned, else element loads with the column clamped to w - 1
-template <typename T>
-__device__ __forceinline__ void load4(const T *__restrict__ p, int r, int c0, int w, bool vec, T (&v)[4])
-{
-    const T *row = p + (int64_t)r * w;
-    if (vec && c0 + 3 < w) {
-        const typename Vec4<T>::type x = *reinterpret_cast<const typename Vec4<T>::type *>(row + c0);
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = x[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = row[min(c0 + k, w - 1)];
-    }
-}
-
-__device__ __forceinline__ bool aligned_rows(const void *p, int w, size_t elem)
-{
-    return reinterpret_cast<uintptr_t>(p) % (4 * elem) == 0 && w % 4 == 0;
-}
-
 // bit (4 i + k): pixel k of the lane's row row0 + i is an inner border pixel -- an in-image 4-neighbour holds another
 // label (a neighbour outside the image is the clamped pixel itself: equal) and the pixel's own label is not 0.
 // The whole wave calls this (the shuffles need every lane).
@@ -58,28 +33,11 @@ template <typename TS>
 __device__ __forceinline__ unsigned border_bits(const void *__restrict__ base, int h, int w, int row0, int rows, int c0, int lane)
 {
     const TS *seg = static_cast<const TS *>(base);
-    const bool vec = aligned_rows(seg, w, sizeof(TS));
-    constexpr int kL = kRowsPerWave + 2;
-    TS v[kL][4], left[kL], right[kL];
-#pragma unroll
-    for (int i = 0; i < kL; i++) load4(seg, min(max(row0 - 1 + i, 0), h - 1), c0, w, vec, v[i]);
-#pragma unroll
-    for (int i = 0; i < kL; i++) {
-        left[i] = shfl_up1(v[i][3]);     // lane - 1's last pixel
-        right[i] = shfl_down1(v[i][0]);  // lane + 1's first pixel
-    }
-    if (lane == 0 || lane == 63) {       // the halo column of the wave's tile
-        const int cc = lane == 0 ? max(c0 - 1, 0) : min(c0 + 4, w - 1);
-#pragma unroll
-        for (int i = 0; i < kL; i++) {
-            const TS x = seg[(int64_t)min(max(row0 - 1 + i, 0), h - 1) * w + cc];
-            if (lane == 0) left[i] = x;
-            else right[i] = x;
-        }
-    }
+    TS v[kTileHaloRows][4], left[kTileHaloRows], right[kTileHaloRows];
+    load_halo_tile(seg, w, h, w, row0, c0, lane, rows_aligned4(seg, w, sizeof(TS)), v, left, right);
     unsigned bits = 0;
 #pragma unroll
-    for (int i = 1; i <= kRowsPerWave; i++) {
+    for (int i = 1; i <= kTileRowsPerWave; i++) {
         if (i > rows) break;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -150,11 +108,11 @@ __global__ __launch_bounds__(256) void overlay_kernel(OverlayArgs a)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int bx = (int)(blockIdx.x % (unsigned)a.col_blocks), by = (int)(blockIdx.x / (unsigned)a.col_blocks);
-    const int row0 = by * kBlockRows + wave * kRowsPerWave;
+    const int row0 = by * kTileBlockRows + wave * kTileRowsPerWave;
     const int h = a.h, w = a.w;
     if (row0 >= h) return;                                   // whole wave: the shuffles below stay inside live waves
-    const int c0 = bx * kWaveCols + lane * 4;
-    const int rows = min(kRowsPerWave, h - row0);
+    const int c0 = bx * kTileWaveCols + lane * 4;
+    const int rows = min(kTileRowsPerWave, h - row0);
 
     const unsigned seg_bits = border_bits_any(a.seg, a.seg_bytes, h, w, row0, rows, c0, lane);
     const unsigned alt_bits = a.alt ? border_bits_any(a.alt, a.alt_bytes, h, w, row0, rows, c0, lane) : 0u;
@@ -162,7 +120,7 @@ __global__ __launch_bounds__(256) void overlay_kernel(OverlayArgs a)
 
     if (a.borders) {
 #pragma unroll
-        for (int i = 0; i < kRowsPerWave; i++) {
+        for (int i = 0; i < kTileRowsPerWave; i++) {
             if (i >= rows) break;
             uint8_t *row = a.borders + (int64_t)(row0 + i) * w;
             const unsigned b4 = (seg_bits >> (4 * i)) & 15u;
@@ -180,17 +138,17 @@ __global__ __launch_bounds__(256) void overlay_kernel(OverlayArgs a)
     if (!a.rgb) return;
 
     // the planes: every load in flight before the first division
-    TP p[3][kRowsPerWave][4];
+    TP p[3][kTileRowsPerWave][4];
 #pragma unroll
     for (int j = 0; j < 3; j++) {
         if (a.ch[j].mode == 0) continue;
         const TP *plane = static_cast<const TP *>(a.ch[j].plane);
-        const bool vec = aligned_rows(plane, w, sizeof(TP));
+        const bool vec = rows_aligned4(plane, w, sizeof(TP));
 #pragma unroll
-        for (int i = 0; i < kRowsPerWave; i++) load4(plane, min(row0 + i, h - 1), c0, w, vec, p[j][i]);
+        for (int i = 0; i < kTileRowsPerWave; i++) load4(plane, w, min(row0 + i, h - 1), c0, w, vec, p[j][i]);
     }
 #pragma unroll
-    for (int i = 0; i < kRowsPerWave; i++) {
+    for (int i = 0; i < kTileRowsPerWave; i++) {
         if (i >= rows) break;
         unsigned px[4][3];
 #pragma unroll
@@ -269,12 +227,6 @@ __global__ __launch_bounds__(256) void colorize_kernel(const TM *__restrict__ ma
     if (bad) atomicOr(status, PXSOM_COLORIZE_BAD_INDEX);
 }
 
-bool overlaps(const void *a, size_t na, const void *b, size_t nb)
-{
-    const char *a0 = static_cast<const char *>(a), *b0 = static_cast<const char *>(b);
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 }  // namespace
 
 PXSOM_EXPORT int pxsom_overlay_rgb(const void *r_dev, const void *g_dev, const void *b_dev, int plane_dtype,
@@ -322,12 +274,13 @@ PXSOM_EXPORT int pxsom_overlay_rgb(const void *r_dev, const void *g_dev, const v
     const size_t seg_bytes = px * pxsom::plane_dtype_bytes(seg_dtype);
     const size_t alt_bytes = alt_dev ? px * pxsom::plane_dtype_bytes(alt_dtype) : 0;
     // the border test reads neighbours another block may already have written
-    if (overlaps(rgb_dev, px * 3, seg_dev, seg_bytes) || overlaps(rgb_dev, px * 3, alt_dev, alt_bytes) ||
-        overlaps(borders_dev, px, seg_dev, seg_bytes) || overlaps(borders_dev, px, alt_dev, alt_bytes) ||
-        overlaps(rgb_dev, px * 3, borders_dev, px))
+    using pxsom::spans_overlap;
+    if (spans_overlap(rgb_dev, px * 3, seg_dev, seg_bytes) || spans_overlap(rgb_dev, px * 3, alt_dev, alt_bytes) ||
+        spans_overlap(borders_dev, px, seg_dev, seg_bytes) || spans_overlap(borders_dev, px, alt_dev, alt_bytes) ||
+        spans_overlap(rgb_dev, px * 3, borders_dev, px))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: an output overlaps a label plane or the other output", fn);
-    const int col_blocks = (w + kWaveCols - 1) / kWaveCols;
-    const int64_t blocks = (int64_t)col_blocks * ((h + kBlockRows - 1) / kBlockRows);
+    const int col_blocks = (w + kTileWaveCols - 1) / kTileWaveCols;
+    const int64_t blocks = (int64_t)col_blocks * ((h + kTileBlockRows - 1) / kTileBlockRows);
     if (blocks > 0x7fffffff) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: image too large", fn);
 
     a.seg = seg_dev;

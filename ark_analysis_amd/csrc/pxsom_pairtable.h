@@ -1,8 +1,7 @@
-// pxsom_pairtable.h -- the run-compressed pair table of K21 (pxsom_nucsplit.hip): an open-addressing table of 64-bit pair
-// keys with an int32 pixel count each, which takes one insertion per RUN of a pair.  It is K18's table (pxsom_merge.hip),
-// which keeps its own copy for now: with the probe loop taken from here its insert_runs_kernel came out with other
-// registers (scripts/compare_device_code.py: 70 SGPRs for 66), and a refactor that changes a measured kernel waits for a
-// measurement.
+// pxsom_pairtable.h -- the run-compressed pair table of K18 (pxsom_merge.hip) and K21 (pxsom_nucsplit.hip): an
+// open-addressing table of 64-bit pair keys with an int32 pixel count each, which takes one insertion per RUN of a pair.
+// (K18's insert_runs_kernel has 70 SGPRs with table_add for the 66 of the probe loop it once spelled out; its stage,
+// pair_overlaps at 2048 x 2048, measured inside the earlier form's own run-to-run spread: profiles/plane_shared/README.md.)
 //
 // A "run" is a stretch of pixels of one pair inside one row and inside one aligned group of 64 pixels of the flat raster
 // order (a wave's pixels): a pure function of the image.  A caller counts the runs first, sizes the table for them
@@ -54,11 +53,20 @@ inline int64_t pair_slots(int64_t capacity)
     return s;
 }
 
-// bytes of the keys (first, 256-aligned) and the counts of a table for `capacity` pairs
+// bytes of the keys of `slots` slots, 256-aligned: the counts follow them
+inline size_t pair_keys_bytes(int64_t slots) { return pxsom::align_up((size_t)slots * sizeof(unsigned long long), 256); }
+
+// bytes of the keys and the counts of a table for `capacity` pairs
 inline size_t pair_table_bytes(int64_t capacity)
 {
     const int64_t slots = pair_slots(capacity);
-    return pxsom::align_up((size_t)slots * sizeof(unsigned long long), 256) + pxsom::align_up((size_t)slots * sizeof(int32_t), 256);
+    return pair_keys_bytes(slots) + pxsom::align_up((size_t)slots * sizeof(int32_t), 256);
+}
+
+// the counts of a table of `slots` slots whose keys start at `keys`
+inline int32_t *pair_table_counts(unsigned long long *keys, int64_t slots)
+{
+    return reinterpret_cast<int32_t *>(reinterpret_cast<char *>(keys) + pair_keys_bytes(slots));
 }
 
 }  // namespace

@@ -25,6 +25,7 @@
 
 #include "pxsom_common.h"
 #include "pxsom_keytable.h"
+#include "pxsom_wave.h"
 
 namespace {
 
@@ -155,17 +156,6 @@ __device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int s
 {
     const int lo = __shfl((int)(unsigned)v, src, 64), hi = __shfl((int)(unsigned)(v >> 32), src, 64);
     return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
-}
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int lo = __shfl_xor((int)(unsigned)(unsigned long long)v, d, 64);
-        const int hi = __shfl_xor((int)(unsigned)((unsigned long long)v >> 32), d, 64);
-        v += (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-    }
-    return v;
 }
 
 // every bit of `open` reachable from a bit of `seed` along a run of set bits (both directions): Kogge-Stone fills
@@ -303,9 +293,9 @@ __global__ __launch_bounds__(256) void hull_kernel(const TI *__restrict__ seg, H
             sum_c = (long long)c0 * len + (long long)(cl + cr) * len / 2;
         }
     }
-    area = wave_sum(area);
-    sum_r = wave_sum(sum_r);
-    sum_c = wave_sum(sum_c);
+    area = pxsom::wave_sum(area);
+    sum_r = pxsom::wave_sum(sum_r);
+    sum_c = pxsom::wave_sum(sum_c);
 
     // concavities: the 4-connected components of the difference image, one flood at a time
     unsigned long long rest = conv & ~m;
@@ -341,10 +331,10 @@ __global__ __launch_bounds__(256) void hull_kernel(const TI *__restrict__ seg, H
         const unsigned long long n4_23 = a1 & ~a2, n4_0 = ~(a0 | a1 | a2), n4_1 = a0 & ~a1 & ~a2;
         const unsigned long long nd_le2 = ~d2 & ~(d1 & d0), nd_1 = d0 & ~d1 & ~d2, nd_2 = d1 & ~d0 & ~d2,
                                  nd_3 = d0 & d1 & ~d2;
-        const long long ca = wave_sum(__popcll(comp));
-        const long long p1 = wave_sum(__popcll(bd & n4_23 & nd_le2));
-        const long long p2 = wave_sum(__popcll(bd & ((n4_0 & nd_2) | (n4_1 & nd_3))));
-        const long long p3 = wave_sum(__popcll(bd & n4_1 & (nd_1 | nd_2)));
+        const long long ca = pxsom::wave_sum(__popcll(comp));
+        const long long p1 = pxsom::wave_sum(__popcll(bd & n4_23 & nd_le2));
+        const long long p2 = pxsom::wave_sum(__popcll(bd & ((n4_0 & nd_2) | (n4_1 & nd_3))));
+        const long long p3 = pxsom::wave_sum(__popcll(bd & n4_1 & (nd_1 | nd_2)));
         const double p = ((double)p1 + (double)p2 * sqrt2) + (double)p3 * half;
         const double ar = (double)ca;
         if ((ar > a.small_min && (p * p) / ar < a.max_compactness) || ar > a.large_min) concavities++;

@@ -98,12 +98,8 @@ __device__ __forceinline__ bool ridge_negative(const double *c, int y, int x, in
     const double hrr = s2 * grad1(g0(-1, 0), g0(0, 0), g0(1, 0), y, H);
     const double hrc = s2 * grad1(g0(0, -1), g0(0, 0), g0(0, 1), x, W);
     const double hcc = s2 * grad1(g1(0, -1), g1(0, 0), g1(0, 1), x, W);
-    const double d = hrr - hcc;
-    const double rt = __dsqrt_rn(d * d + 4.0 * (hrc * hrc));
-    const double t = hrr + hcc;
-    const double e_hi = (t + rt) / 2.0, e_lo = (t - rt) / 2.0;
-    const bool lo_big = fabs(e_lo) >= fabs(e_hi);
-    const double big = lo_big ? e_lo : e_hi, small = lo_big ? e_hi : e_lo;
+    double big, small;
+    hessian_eigenvalues(hrr, hrc, hcc, big, small);
     return big + alpha * small < 0.0;
 }
 
@@ -187,9 +183,8 @@ PXSOM_EXPORT int pxsom_ridge_sign(const uint8_t *fg_dev, int h, int w, int64_t l
             return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: factor %g of scale %d is not a finite positive number", fn, scales_host[s], s);
     }
     {   // out must not share a byte with fg
-        const uintptr_t f0 = reinterpret_cast<uintptr_t>(fg_dev), f1 = f0 + (uintptr_t)(h - 1) * (uintptr_t)ld + (uintptr_t)w;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev), o1 = o0 + (uintptr_t)(h - 1) * (uintptr_t)ldo + (uintptr_t)w;
-        if (o0 < f1 && f0 < o1) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps fg", fn);
+        if (pxsom::spans_overlap(out_dev, pxsom::plane_span_bytes(h, w, ldo, 1), fg_dev, pxsom::plane_span_bytes(h, w, ld, 1)))
+            return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps fg", fn);
     }
     for (int s = 0; s < n_scales; s++)
         if (radii_host[s] > kRidgeMaxRadius)

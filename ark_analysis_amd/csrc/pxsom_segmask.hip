@@ -4,9 +4,10 @@
 //                   then mapping.get((int32)label, unassigned) (relabel_segmentation) and the output cast
 //                   (ark/utils/data_utils.py:70-84, 204-335 of the reference)
 //
-// One fused pass.  A block is 4 waves; each wave owns a 256-column x kRowsPerWave-row tile, every lane 4 consecutive
-// pixels of a row (one 4-, 8-, 16- or 32-byte load per row, one packed store per row).  With erosion a wave loads
-// kRowsPerWave + 2 rows up front (the one-row halo above and below comes from L1 / L2: it is the neighbouring wave's or
+// One fused pass over the tile of pxsom_plane.h, which K29 shares.  A block is 4 waves; each wave owns 256 columns x
+// kTileRowsPerWave rows, every lane 4 consecutive pixels of a row (one 4-, 8-, 16- or 32-byte load per row, one packed
+// store per row).  With erosion a wave loads
+// kTileRowsPerWave + 2 rows up front (the one-row halo above and below comes from L1 / L2: it is the neighbouring wave's or
 // block's own row, read there in the same sweep, so HBM sees each input byte about once); the left / right halo column
 // comes from the neighbouring lane by a cross-lane shuffle, and only lanes 0 and 63 load one extra element per row.
 // No LDS staging: the halo re-read is 2 of 6 rows and served by the caches, and the shuffle replaces the LDS round trip
@@ -19,28 +20,6 @@
 #include "pxsom_keytable.h"
 
 namespace {
-
-constexpr int kWaveCols = 256;       // 64 lanes x 4 pixels
-constexpr int kRowsPerWave = 4;
-constexpr int kWaves = 4;
-constexpr int kBlockRows = kRowsPerWave * kWaves;
-
-// 4 labels of row r from column c0: one wide load when the 4 lie inside the row and the rows are aligned, else element
-// loads with the column clamped to w - 1 (the clamp is scipy's reflect at distance 1: the right neighbour of the last
-// column is the column itself)
-template <typename TI>
-__device__ __forceinline__ void load_row(const TI *__restrict__ seg, int64_t ld, int r, int c0, int w, bool vec, TI (&v)[4])
-{
-    const TI *row = seg + (int64_t)r * ld;
-    if (vec && c0 + 3 < w) {
-        const typename Vec4<TI>::type x = *reinterpret_cast<const typename Vec4<TI>::type *>(row + c0);
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = x[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = row[min(c0 + k, w - 1)];
-    }
-}
 
 template <typename TV>
 struct Table {
@@ -63,22 +42,6 @@ __device__ __forceinline__ TO finish(const Table<TV> &t, TI label)
     return (TO)lookup<TV, TI>(t, label);
 }
 
-template <typename TO>
-__device__ __forceinline__ void store_row(TO *__restrict__ out, int64_t ldo, int r, int c0, int w, bool vec, const TO (&o)[4])
-{
-    TO *row = out + (int64_t)r * ldo;
-    if (vec && c0 + 3 < w) {
-        typename Vec4<TO>::type x;
-#pragma unroll
-        for (int k = 0; k < 4; k++) x[k] = o[k];
-        *reinterpret_cast<typename Vec4<TO>::type *>(row + c0) = x;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (c0 + k < w) row[c0 + k] = o[k];
-    }
-}
-
 template <typename TI, typename TO, typename TV>
 __global__ __launch_bounds__(256) void segmask_kernel(const TI *__restrict__ seg, int h, int w, int64_t ld, int erode_mode,
                                                       int conn8, int64_t background, Table<TV> table, TO *__restrict__ out,
@@ -86,31 +49,33 @@ __global__ __launch_bounds__(256) void segmask_kernel(const TI *__restrict__ seg
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int bx = (int)(blockIdx.x % (unsigned)col_blocks), by = (int)(blockIdx.x / (unsigned)col_blocks);
-    const int row0 = by * kBlockRows + wave * kRowsPerWave;
+    const int row0 = by * kTileBlockRows + wave * kTileRowsPerWave;
     if (row0 >= h) return;                                   // whole wave: the shuffles below stay inside live waves
-    const int c0 = bx * kWaveCols + lane * 4;
-    const int rows = min(kRowsPerWave, h - row0);
+    const int c0 = bx * kTileWaveCols + lane * 4;
+    const int rows = min(kTileRowsPerWave, h - row0);
 
     if (erode_mode == PXSOM_SEG_ERODE_NONE) {
-        TI v[kRowsPerWave][4];
+        TI v[kTileRowsPerWave][4];
 #pragma unroll
-        for (int i = 0; i < kRowsPerWave; i++) load_row(seg, ld, min(row0 + i, h - 1), c0, w, vec_in, v[i]);
+        for (int i = 0; i < kTileRowsPerWave; i++) load4(seg, ld, min(row0 + i, h - 1), c0, w, vec_in, v[i]);
 #pragma unroll
-        for (int i = 0; i < kRowsPerWave; i++) {
+        for (int i = 0; i < kTileRowsPerWave; i++) {
             if (i >= rows) break;
             TO o[4];
 #pragma unroll
             for (int k = 0; k < 4; k++) o[k] = finish<TI, TO, TV>(table, v[i][k]);
-            store_row(out, ldo, row0 + i, c0, w, vec_out, o);
+            store4(out, ldo, row0 + i, c0, w, vec_out, o);
         }
         return;
     }
 
-    // rows row0 - 1 .. row0 + kRowsPerWave, clamped into the image (reflect at distance 1), all loads in flight at once
-    constexpr int kL = kRowsPerWave + 2;
+    // load_halo_tile (pxsom_plane.h) written out: through the helper every instantiation came out with 2 to 4 fewer VGPRs and
+    // other scheduling, and at 2048 x 2048 three of four cases measured 0.2 - 0.4 % beyond the parent's own run-to-run spread
+    // (profiles/plane_shared/README.md).  This form compiles to the code it had.
+    constexpr int kL = kTileHaloRows;
     TI v[kL][4], left[kL], right[kL];
 #pragma unroll
-    for (int i = 0; i < kL; i++) load_row(seg, ld, min(max(row0 - 1 + i, 0), h - 1), c0, w, vec_in, v[i]);
+    for (int i = 0; i < kL; i++) load4(seg, ld, min(max(row0 - 1 + i, 0), h - 1), c0, w, vec_in, v[i]);
 #pragma unroll
     for (int i = 0; i < kL; i++) {
         left[i] = shfl_up1(v[i][3]);     // lane - 1's last pixel
@@ -126,7 +91,7 @@ __global__ __launch_bounds__(256) void segmask_kernel(const TI *__restrict__ seg
         }
     }
 #pragma unroll
-    for (int i = 1; i <= kRowsPerWave; i++) {
+    for (int i = 1; i <= kTileRowsPerWave; i++) {
         if (i > rows) break;
         TO o[4];
 #pragma unroll
@@ -140,7 +105,7 @@ __global__ __launch_bounds__(256) void segmask_kernel(const TI *__restrict__ seg
             if (erode_mode == PXSOM_SEG_ERODE_INNER) edge &= (int64_t)c != background;
             o[k] = finish<TI, TO, TV>(table, edge ? (TI)0 : c);
         }
-        store_row(out, ldo, row0 + i - 1, c0, w, vec_out, o);
+        store4(out, ldo, row0 + i - 1, c0, w, vec_out, o);
     }
 }
 
@@ -163,12 +128,9 @@ int launch_typed(const Launch &a)
 {
     typedef typename std::conditional<std::is_same<TO, double>::value, double, int32_t>::type TV;
     const Table<TV> t{a.keys, reinterpret_cast<const TV *>(a.values), (TV)a.unassigned};
-    const auto aligned = [](const void *p, int64_t stride, size_t vbytes) {
-        return (reinterpret_cast<uintptr_t>(p) % vbytes) == 0 && stride % 4 == 0;
-    };
-    const bool vec_in = aligned(a.seg, a.ld, 4 * sizeof(TI)), vec_out = aligned(a.out, a.ldo, 4 * sizeof(TO));
-    const int col_blocks = (a.w + kWaveCols - 1) / kWaveCols;
-    const int64_t blocks = (int64_t)col_blocks * ((a.h + kBlockRows - 1) / kBlockRows);
+    const bool vec_in = rows_aligned4(a.seg, a.ld, sizeof(TI)), vec_out = rows_aligned4(a.out, a.ldo, sizeof(TO));
+    const int col_blocks = (a.w + kTileWaveCols - 1) / kTileWaveCols;
+    const int64_t blocks = (int64_t)col_blocks * ((a.h + kTileBlockRows - 1) / kTileBlockRows);
     if (blocks > 0x7fffffff) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "pxsom_segmask: image too large");
     PXSOM_TIMED_LAUNCH((segmask_kernel<TI, TO, TV>), dim3((unsigned)blocks), dim3(256), 0, a.st,
                        reinterpret_cast<const TI *>(a.seg), a.h, a.w, a.ld, a.erode_mode, a.conn8, a.background, t,
@@ -220,10 +182,9 @@ PXSOM_EXPORT int pxsom_segmask(const void *seg_dev, int seg_dtype, int h, int w,
           unassigned <= 2147483647.0))
         return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: unassigned %g is not an int32 value", fn, unassigned);
     if (erode_mode != PXSOM_SEG_ERODE_NONE) {   // erosion reads neighbours another block may already have written
-        const char *s0 = static_cast<const char *>(seg_dev), *o0 = static_cast<const char *>(out_dev);
-        const char *s1 = s0 + ((int64_t)(h - 1) * ld + w) * pxsom::plane_dtype_bytes(seg_dtype);
-        const char *o1 = o0 + ((int64_t)(h - 1) * ldo + w) * pxsom::plane_dtype_bytes(out_dtype);
-        if (s0 < o1 && o0 < s1) return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps seg under erosion", fn);
+        if (pxsom::spans_overlap(seg_dev, pxsom::plane_span_bytes(h, w, ld, pxsom::plane_dtype_bytes(seg_dtype)), out_dev,
+                                 pxsom::plane_span_bytes(h, w, ldo, pxsom::plane_dtype_bytes(out_dtype))))
+            return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps seg under erosion", fn);
     }
     const size_t need = n_keys > 0 && !(flags & PXSOM_SEGMASK_FORCE_SEARCH)
                             ? pxsom_segmask_workspace_bytes(n_keys, key_min, key_max) : 0;

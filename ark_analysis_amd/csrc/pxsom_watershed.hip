@@ -28,6 +28,7 @@
 #include <cstdint>
 
 #include "pxsom_common.h"
+#include "pxsom_plane.h"
 
 namespace {
 
@@ -486,12 +487,6 @@ Layout layout(int h, int w)
     return l;
 }
 
-bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -518,9 +513,9 @@ PXSOM_EXPORT int pxsom_watershed(const int32_t *elev_dev, int64_t lde, const int
     if (pxsom_label_components_workspace_bytes(h, w) == 0)
         return pxsom::fail(PXSOM_ERR_UNSUPPORTED, "%s: %d x %d pixels are beyond what pxsom_label_components takes", fn, h, w);
     {   // the labels grow in out while both inputs are still read
-        const size_t out_bytes = ((size_t)(h - 1) * (size_t)ldo + (size_t)w) * 4;
-        if (overlaps(out_dev, out_bytes, elev_dev, ((size_t)(h - 1) * (size_t)lde + (size_t)w) * 4) ||
-            overlaps(out_dev, out_bytes, markers_dev, ((size_t)(h - 1) * (size_t)ldm + (size_t)w) * 4))
+        const size_t out_bytes = pxsom::plane_span_bytes(h, w, ldo, 4);
+        if (pxsom::spans_overlap(out_dev, out_bytes, elev_dev, pxsom::plane_span_bytes(h, w, lde, 4)) ||
+            pxsom::spans_overlap(out_dev, out_bytes, markers_dev, pxsom::plane_span_bytes(h, w, ldm, 4)))
             return pxsom::fail(PXSOM_ERR_INVALID_ARG, "%s: out overlaps an input", fn);
     }
     const Layout l = layout(h, w);

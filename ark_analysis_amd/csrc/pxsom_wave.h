@@ -52,6 +52,14 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v)
     return min(r[0], r[1]);
 }
 
+// wave-wide sum of a 64-bit integer, result in every lane (a butterfly of shuffles: off the critical path where it is used)
+__device__ __forceinline__ long long wave_sum(long long v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 // value of the lane to the left inside a 16-lane row (row_shr:1); lane 0 of a row keeps its own
 __device__ __forceinline__ double shr1_f64(double v)
 {

@@ -47,7 +47,7 @@ SEG_F64 = 6
 # pxsom_gaussian_blur_plane / pxsom_zero_by_seg: the plane dtypes (PXSOM_SEG_* codes, float32 = PXSOM_SEG_F32)
 PLANE_DTYPES = {torch.uint8: 0, torch.int16: 1, torch.uint16: 2, torch.int32: 3, torch.float32: 7}
 PLANE_MODE_DTYPES = {**PLANE_DTYPES, torch.float64: 6}
-PAIR_CAPACITY_MAX = 1 << 27                          # kMaxPairCapacity of csrc/pxsom_merge.hip
+PAIR_CAPACITY_MAX = 1 << 27                          # kMaxPairCapacity of csrc/pxsom_pairtable.h
 
 
 def _binary_plane(fg: torch.Tensor, what: str) -> torch.Tensor:
@@ -84,6 +84,37 @@ def _like_plane(t: Optional[torch.Tensor], plane: torch.Tensor, what: str) -> to
 
 def _ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _f64_plane(plane: torch.Tensor, what: str):
+    """``(h, w, ld)`` of a non-empty ``[H, W]`` float64 HBM plane with contiguous rows (any row stride)."""
+    if plane.dim() != 2 or not plane.is_cuda or plane.dtype != torch.float64:
+        raise ValueError("%s must be a 2-D float64 HBM tensor" % what)
+    h, w = plane.shape
+    if h == 0 or w == 0:
+        raise ValueError("%s must not be empty" % what)
+    if w > 1 and plane.stride(1) != 1:
+        raise ValueError("%s rows must be contiguous (stride(1) == 1)" % what)
+    return h, w, _ld(plane)
+
+
+def _image_plane(plane: torch.Tensor, what: str):
+    if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in PLANE_DTYPES:
+        raise ValueError("%s must be a contiguous 2-D uint8 / int16 / uint16 / int32 / float32 HBM tensor" % what)
+    if plane.numel() == 0:
+        raise ValueError("%s must not be empty" % what)
+    return plane.shape
+
+
+def _byte_range(t: torch.Tensor):
+    return t.data_ptr(), t.data_ptr() + ((t.shape[0] - 1) * _ld(t) + t.shape[1]) * t.element_size()
+
+
+def _check_apart(out: torch.Tensor, plane: torch.Tensor, why: str, what: str = "the input") -> None:
+    lo, hi = _byte_range(out)
+    plo, phi = _byte_range(plane)
+    if lo < phi and plo < hi:
+        raise ValueError("out must not share memory with %s: %s" % (what, why))
 
 
 def _label_pair(a: torch.Tensor, b: torch.Tensor):

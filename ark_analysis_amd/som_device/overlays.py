@@ -6,20 +6,12 @@ import numpy as np
 import torch
 
 from .. import _capi
-from ._args import PLANE_DTYPES, SEG_DTYPES, _label_image
+from ._args import PLANE_DTYPES, SEG_DTYPES, _image_plane, _label_image
 from .pixels import quantile_nonzero
 
 OVERLAY_ZERO, OVERLAY_RESCALE, OVERLAY_CLIP = 0, 1, 2     # include/pxsom.h PXSOM_OVERLAY_*
 COLORIZE_BAD_INDEX = 1                                    # PXSOM_COLORIZE_BAD_INDEX
 COLORIZE_MASK_DTYPES = {torch.uint8: 0, torch.int16: 1, torch.uint16: 2, torch.int32: 3}   # PXSOM_SEG_* codes
-
-
-def _image_plane(plane: torch.Tensor, what: str):
-    if plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous() or plane.dtype not in PLANE_DTYPES:
-        raise ValueError("%s must be a contiguous 2-D uint8 / int16 / uint16 / int32 / float32 HBM tensor" % what)
-    if plane.numel() == 0:
-        raise ValueError("%s must not be empty" % what)
-    return plane.shape
 
 
 def _as_float64_column(plane: torch.Tensor) -> torch.Tensor:

@@ -8,8 +8,8 @@ import numpy as np
 import torch
 
 from .. import _capi
-from ._args import (PAIR_CAPACITY_MAX, PLANE_DTYPES, PLANE_MODE_DTYPES, SEG_DTYPES, SEG_F64, _binary_plane, _label_image,
-                    _label_pair, _label_plane, _ld, _like_plane, _rows_plane)
+from ._args import (PAIR_CAPACITY_MAX, PLANE_DTYPES, PLANE_MODE_DTYPES, SEG_DTYPES, SEG_F64, _binary_plane, _check_apart,
+                    _f64_plane, _label_image, _label_pair, _label_plane, _ld, _like_plane, _rows_plane)
 from .pixels import gaussian_kernel1d, quantile_f32, quantile_nonzero
 
 
@@ -485,18 +485,6 @@ HISTOGRAM_MAX_BINS = 1024                            # kMaxBins of csrc/pxsom_ma
 EDT_NO_BACKGROUND = "the plane has no background pixel: the distance transform is undefined"
 
 
-def _f64_plane(plane: torch.Tensor, what: str):
-    """``(h, w, ld)`` of a non-empty ``[H, W]`` float64 HBM plane with contiguous rows (any row stride)."""
-    if plane.dim() != 2 or not plane.is_cuda or plane.dtype != torch.float64:
-        raise ValueError("%s must be a 2-D float64 HBM tensor" % what)
-    h, w = plane.shape
-    if h == 0 or w == 0:
-        raise ValueError("%s must not be empty" % what)
-    if w > 1 and plane.stride(1) != 1:
-        raise ValueError("%s rows must be contiguous (stride(1) == 1)" % what)
-    return h, w, _ld(plane)
-
-
 def plane_greater(plane: torch.Tensor, level: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``plane > level`` of a ``[H, W]`` float64 HBM plane as uint8 1 / 0 (pxsom_plane_greater); a NaN pixel is 0."""
     h, w, ld = _f64_plane(plane, "plane")
@@ -664,10 +652,6 @@ def frangi_arguments(sigmas, beta, gamma, black_ridges=False):
     return [float(s) for s in flat], 2.0 * beta * beta, 2.0 * gamma * gamma
 
 
-def _byte_range(t: torch.Tensor):
-    return t.data_ptr(), t.data_ptr() + ((t.shape[0] - 1) * _ld(t) + t.shape[1]) * t.element_size()
-
-
 def frangi(plane: torch.Tensor, sigmas=FRANGI_SIGMAS, beta=0.5, gamma=15.0, scale=1.0,
            out: Optional[torch.Tensor] = None, black_ridges: bool = False) -> torch.Tensor:
     """``skimage.filters.frangi(plane, sigmas, beta=beta, gamma=gamma, black_ridges=False, mode="reflect") * scale`` in
@@ -684,10 +668,7 @@ def frangi(plane: torch.Tensor, sigmas=FRANGI_SIGMAS, beta=0.5, gamma=15.0, scal
     if not np.isfinite(scale):
         raise ValueError("scale must be finite, got %r" % (scale,))
     out = _rows_plane(out, h, w, torch.float64, plane.device, "out")
-    lo, hi = _byte_range(out)
-    plo, phi = _byte_range(plane)
-    if lo < phi and plo < hi:
-        raise ValueError("out must not share memory with the plane: every scale blurs the plane again")
+    _check_apart(out, plane, "every scale blurs the plane again", what="the plane")
     x = plane.contiguous()                           # the blur takes contiguous planes
     g, tmp = torch.empty_like(x), torch.empty_like(x)
     for i, sigma in enumerate(sigmas):
@@ -739,13 +720,6 @@ def clahe_arguments(shape, kernel_size, clip_limit=0.01, nbins=256):
     ke = k * k
     clim = int(np.clip(clip_limit * ke, 1, None)) if clip_limit > 0.0 else CLAHE_GREY_LEVELS
     return k, clim, (CLAHE_GREY_LEVELS - 1) / ke
-
-
-def _check_apart(out: torch.Tensor, plane: torch.Tensor, why: str) -> None:
-    lo, hi = _byte_range(out)
-    plo, phi = _byte_range(plane)
-    if lo < phi and plo < hi:
-        raise ValueError("out must not share memory with the input: " + why)
 
 
 def _equalize_gray(gray: torch.Tensor, k: int, clim: int, map_scale: float, out, maps_out, raw_out) -> torch.Tensor:

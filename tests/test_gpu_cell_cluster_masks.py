@@ -92,7 +92,9 @@ def test_every_dtype_erosion_and_output(gpu, dt):
         _check(gpu, seg, erode, conn, 0, keys, values, -3, npdt)            # lookup into the input dtype
 
 
-@pytest.mark.parametrize("shape", [(1, 1), (1, 7), (1, 1030), (9, 1), (1025, 1), (17, 33), (300, 517), (33, 260)])
+# (the last four: one below, at and one above the wave's 256 columns and 4 rows, and the block's 16 rows)
+@pytest.mark.parametrize("shape", [(1, 1), (1, 7), (1, 1030), (9, 1), (1025, 1), (17, 33), (300, 517), (33, 260), (3, 255),
+                                   (4, 256), (5, 257), (16, 256)])
 def test_shapes(gpu, shape):
     rs = np.random.RandomState(sum(shape))
     for dt in ("u8", "i32", "i64"):

@@ -19,20 +19,27 @@ LABEL_DTYPES = (np.uint8, np.int32, np.int64)
 SHAPES = ((1, 1), (1, 7), (7, 1), (2, 2), (3, 255), (4, 256), (5, 257), (17, 258), (16, 513), (67, 131))
 
 
-def _up(a, gpu):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
+def _up(a, gpu, shift=0):
+    """The array in HBM, contiguous; with ``shift`` that many elements into its allocation (a base off 16 bytes)."""
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
+    if shift:
+        flat = torch.empty(t.numel() + shift, dtype=t.dtype, device=gpu)
+        flat[shift:] = t.reshape(-1)
+        t = flat[shift:].view(t.shape)
+    return t
 
 
 def _cells(h, w, seed, dtype, big=False):
     return ovr.cells(h, w, seed, dtype, big=big and np.dtype(dtype).itemsize >= 4)
 
 
-def _check(gpu, planes, seg, alt=None):
-    """overlay_rgb with and without the border plane against the statement."""
+def _check(gpu, planes, seg, alt=None, shift=0):
+    """overlay_rgb with and without the border plane against the statement; with ``shift`` every input plane (an
+    ``[H, W, c]`` image as its c planes) starts that many elements into its allocation."""
     from ark_analysis_amd import som_device as sd
     want = ovr.overlay(planes, seg, alt)
-    dev_planes = _up(planes, gpu)
-    seg_d, alt_d = _up(seg, gpu), None if alt is None else _up(alt, gpu)
+    dev_planes = [_up(planes[..., i], gpu, shift) for i in range(planes.shape[2])] if shift else _up(planes, gpu)
+    seg_d, alt_d = _up(seg, gpu, shift), None if alt is None else _up(alt, gpu, shift)
     got, borders = sd.overlay_rgb(dev_planes, seg_d, alt_d, want_borders=True)
     assert got.dtype == torch.uint8 and tuple(got.shape) == seg.shape + (3,)
     assert np.array_equal(got.cpu().numpy(), want)
@@ -51,6 +58,19 @@ def test_overlay_shapes(gpu, shape):
         seg = _cells(h, w, seed, LABEL_DTYPES[n % 3], big=True)
         alt = _cells(h, w, seed + 7, LABEL_DTYPES[(n + 1) % 3]) if n % 2 == 0 else None
         _check(gpu, planes, seg, alt)
+
+
+def test_overlay_unaligned_base(gpu):
+    """Widths that are a multiple of 4, so that only the base pointer decides between the 4-element and the element
+    loads: every plane and label plane one and three elements off its allocation."""
+    h, w = 5, 256
+    for n, pdt in enumerate(PLANE_DTYPES):
+        planes = np.stack([ovr.signal(h, w, 300 + n + i, pdt) for i in range(2)], axis=-1)
+        seg = _cells(h, w, 310 + n, LABEL_DTYPES[n % 3], big=True)
+        alt = _cells(h, w, 320 + n, LABEL_DTYPES[(n + 1) % 3])
+        for shift in (1, 3):
+            assert _up(seg, gpu, shift).data_ptr() % (4 * seg.dtype.itemsize) != 0
+            _check(gpu, planes, seg, alt, shift=shift)
 
 
 @pytest.mark.parametrize("ldt", LABEL_DTYPES, ids=lambda d: np.dtype(d).name)
