@@ -173,6 +173,12 @@ SYMBOLS = {
     "pxsom_percentile_f32_listq": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     "pxsom_overlay_rgb": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pxsom_colorize": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pxsom_tsne_workspace_bytes": (_sz, [_i64]),
+    "pxsom_column_moments": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "pxsom_project_rows": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pxsom_pair_sqdist_f32": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "pxsom_tsne_affinities": (_i32, [_vp, _i64, _f64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pxsom_tsne_step": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -33,6 +33,9 @@ from .planes import (CLAHE_GREY_LEVELS, CLAHE_NBINS, channel_watershed_inputs, c
 from .planes import WATERSHED_STATS, channel_fiber_labels, watershed
 from .overlays import (COLORIZE_BAD_INDEX, COLORIZE_MASK_DTYPES, OVERLAY_CLIP, OVERLAY_RESCALE, OVERLAY_ZERO, colorize,
                        overlay_compose, overlay_ranges, overlay_rgb, percentiles_positive)
+from .embedding import (TSNE_MAX_ROWS, TsneResult, column_moments, pair_sqdist_f32, pca_scores, principal_axes,
+                        project_rows, tsne, tsne_affinities, tsne_embed, tsne_learning_rate, tsne_max_rows, tsne_step,
+                        tsne_workspace_bytes)
 from .cells import (CELLQUANT_FORCE_SEARCH, CELLQUANT_IMAGE_DTYPES, CELLQUANT_MODES, CELLQUANT_NUC_CAPACITY,
                     CONCAVITY_DEFAULTS, NUCSPLIT_FORCE_SEARCH, REGION_FORCE_SEARCH, REGION_MAX_SIDE, cell_quantify,
                     choose_splits, label_keys, nuclear_overlaps, region_euler, region_moments, region_props,

@@ -1223,6 +1223,58 @@ int pxsom_overlay_rgb(const void *r_dev, const void *g_dev, const void *b_dev, i
 int pxsom_colorize(const void *mask_dev, int mask_dtype, int h, int w, const uint8_t *table_dev, int n_rows, int n_cols,
                    uint8_t *out_dev, int32_t *status_dev, void *stream);
 
+/* ---- PCA scores and exact t-SNE of the cell table (K30) ------------------------------------------------------------------
+ * reference: ark/analysis/dimensionality_reduction.py visualize_dimensionality_reduction, which hands the marker columns
+ * to sklearn's PCA() or TSNE().  Symbols added under ABI 9, none changed.  tests/tsne_reference.py is the same statement in
+ * numpy, pinned to scikit-learn 1.7.2 itself by tests/test_tsne.py.  All arithmetic is binary64, no floating-point atomic,
+ * no waiting between workgroups; every sum runs over a fixed partition in a fixed order (csrc/pxsom_embed.hip states it),
+ * so the same input gives the same bits on every run.  x_dev is a contiguous [n, c] matrix of dtype PXSOM_F32 or PXSOM_F64.
+ *
+ * pxsom_column_moments: mean_dev [c] and cov_dev [c, c] (centred products over n - 1; two passes; rows in blocks of 256
+ * folded in block order).  2 <= c <= PXSOM_MAX_CHANNELS, n >= 2.  cov is exactly symmetric.
+ * pxsom_project_rows: scores_dev [n, 2] = (x - mean) . axes_dev [2, c], channels ascending.
+ * pxsom_pair_sqdist_f32: d2_dev [n, n] float32, d2[i, j] = sum_t (x_it - x_jt)^2 in binary64, t ascending, one rounding per
+ * operation, then one rounding to float32 (sklearn's cast in _joint_probabilities); the diagonal is 0.
+ *
+ * pxsom_tsne_affinities: per row the search of sklearn/manifold/_utils.pyx _binary_search_perplexity as written there
+ * (beta from 1, at most 100 evaluations, doubling or halving while a bound is infinite, then bisection, stop at
+ * |H - log perplexity| <= 1e-5; 1e-5, 1e-8 and the perplexity taken as the binary32 nearest to them; j = i left out; a
+ * zero sum replaced by 1e-8).  joint = 0 leaves the conditional rows in p_dev [n, n]; joint != 0 goes on to
+ * P = max((Pc + Pc^T) / max(sum P, eps), eps), eps = 2^-52, in place (the dense form of _joint_probabilities; the
+ * diagonal holds eps and no sum reads it).  beta_dev [n] and steps_dev [n] (the index of the last evaluation) say which
+ * path each row took.
+ *
+ * pxsom_tsne_step: one iteration of sklearn's _gradient_descent on _kl_divergence for two components (one degree of
+ * freedom), three launches in stream order and a fourth with want_error:
+ *   Z = sum_{i != j} n_ij, n_ij = 1 / (1 + |y_i - y_j|^2): row sums, then one workgroup folds them into the one Z that
+ *   every workgroup of the gradient launch reads;
+ *   q_ij = max(n_ij * (1 / Z), eps), the reciprocal formed once per thread (two roundings where n_ij / Z has one);
+ *   grad_i = 4 sum_j (e p_ij - q_ij) n_ij (y_i - y_j), a stream over P (each row read once);
+ *   with want_error: error = sum_{i != j} e p_ij log(max(e p_ij, eps) / q_ij) and the norm of grad * gains, into
+ *   error_and_gradnorm_dev [2];
+ *   then per parameter, one rounding per operation: gains += 0.2 where update * grad < 0, else gains *= 0.8;
+ *   gains = max(gains, min_gain); grad *= gains; update = momentum * update - learning_rate * grad; y_out = y_in + update.
+ * e is the scalar `exaggeration`; P is never rewritten.  y_in_dev and y_out_dev are different [n, 2] buffers (y_in 16-byte
+ * aligned); update_dev and gains_dev [n, 2] are updated in place; grad_dev is NULL or gets the gradient [n, 2] before the
+ * gains.
+ *
+ * workspace: pxsom_tsne_workspace_bytes(n) bytes (0 for a refused n), 16-byte aligned, for both entries; P (8 n^2 bytes) and
+ * d2 (4 n^2 bytes) are the caller's.  2 <= n <= PXSOM_TSNE_MAX_ROWS.  Sizes outside the limits: PXSOM_ERR_UNSUPPORTED; null
+ * pointers, misalignment, y_in == y_out, non-finite parameters: PXSOM_ERR_INVALID_ARG; a short, null or misaligned
+ * workspace: PXSOM_ERR_WORKSPACE; all before any HIP call. */
+#define PXSOM_TSNE_MAX_ROWS 1048576
+size_t pxsom_tsne_workspace_bytes(int64_t n);
+int pxsom_column_moments(const void *x_dev, int64_t n, int c, int dtype, double *mean_dev, double *cov_dev, void *stream);
+int pxsom_project_rows(const void *x_dev, int64_t n, int c, int dtype, const double *mean_dev, const double *axes_dev,
+                       double *scores_dev, void *stream);
+int pxsom_pair_sqdist_f32(const void *x_dev, int64_t n, int c, int dtype, float *d2_dev, void *stream);
+int pxsom_tsne_affinities(const float *d2_dev, int64_t n, double perplexity, int joint, double *beta_dev, int32_t *steps_dev,
+                          double *p_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int pxsom_tsne_step(const double *p_dev, int64_t n, const double *y_in_dev, double *y_out_dev, double *update_dev,
+                    double *gains_dev, double exaggeration, double momentum, double learning_rate, double min_gain,
+                    int want_error, double *error_and_gradnorm_dev, double *grad_dev, void *workspace_dev,
+                    size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
