@@ -94,22 +94,42 @@ def tif_overlay_preprocess(plotting_tif):
     return np.flip(out, axis=2)
 
 
+OVERLAY_ZERO, OVERLAY_RESCALE, OVERLAY_CLIP = 0, 1, 2      # include/pxsom.h PXSOM_OVERLAY_*
+
+
+def compose(planes, modes, ranges, seg, alt=None, recalled=None):
+    """pxsom_overlay_rgb as include/pxsom.h states it: output byte j (red, green, blue) is 0 under mode OVERLAY_ZERO
+    (``planes[j]`` may be None), else rescale_intensity of ``planes[j]`` over ``ranges[j] = (lo, hi)`` -- OVERLAY_RESCALE
+    with lo < hi, OVERLAY_CLIP with lo == hi; then the white border of ``seg`` and the red one of ``alt`` -> uint8
+    [H, W, 3]."""
+    seg = np.asarray(seg)
+    out = np.zeros(seg.shape + (3,), dtype=np.uint8)
+    for j in range(3):
+        if modes[j] == OVERLAY_ZERO:
+            continue
+        lo, hi = ranges[j]
+        assert (lo < hi) if modes[j] == OVERLAY_RESCALE else (modes[j] == OVERLAY_CLIP and lo == hi)
+        out[:, :, j] = rescale_intensity_uint8(np.asarray(planes[j]), lo, hi, recalled)
+    out[inner_boundaries(seg), :] = 255
+    if alt is not None:
+        edge = inner_boundaries(alt)
+        out[edge, 0] = 255
+        out[edge, 1:] = 0
+    return out
+
+
 def overlay(plotting_tif, seg, alt=None, recalled=None):
-    """create_overlay from the arrays on: uint8 [H, W, 3]."""
+    """create_overlay from the arrays on: uint8 [H, W, 3].  A channel with a zero maximum stays zero; every other one is
+    rescaled from the 5th .. 95th percentile of its positive pixels."""
     tif = tif_overlay_preprocess(plotting_tif)
-    rescaled = np.zeros(tif.shape, dtype=np.uint8)
+    modes, ranges = [OVERLAY_ZERO] * 3, [(0.0, 0.0)] * 3
     for idx in range(3):
         plane = tif[:, :, idx]
         if np.max(plane) == 0:
             continue
         lo, hi = percentiles_positive(plane)
-        rescaled[:, :, idx] = rescale_intensity_uint8(plane, lo, hi, recalled)
-    rescaled[inner_boundaries(seg), :] = 255
-    if alt is not None:
-        edge = inner_boundaries(alt)
-        rescaled[edge, 0] = 255
-        rescaled[edge, 1:] = 0
-    return rescaled
+        modes[idx], ranges[idx] = (OVERLAY_CLIP if lo == hi else OVERLAY_RESCALE), (lo, hi)
+    return compose([tif[:, :, idx] for idx in range(3)], modes, ranges, seg, alt, recalled)
 
 
 def deepcell_pages(stack, nuc_idx, mem_idx):

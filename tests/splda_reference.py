@@ -2,8 +2,9 @@
 written from the statement of what spatial_lda's featurize_samples is taken to do -- not from any library's code.
 
 neighborhood_sums: per row, the mask over its FOV's rows is ``np.sqrt(dx * dx + dy * dy) < radius`` (``<=`` when
-closed); the count is the mask's sum and the sums are the last row of ``feats[mask].cumsum(axis=0)`` -- a cumulative sum
-is the sequential fold in row order, which ``np.add.reduce`` (pairwise) is not.
+closed); the count is the mask's sum and the sums are the last row of the cumulative sum of a row of +0.0 followed by
+``feats[mask]`` -- a cumulative sum is the sequential fold in row order, which ``np.add.reduce`` (pairwise) is not, and
+the fold starts from +0.0 as include/pxsom.h states it: members that are all -0.0 sum to +0.0.
 
 featurize: one pandas sub-frame per anchor cell, as the featurisations are worded: cells per cluster value, cells with a
 marker above 0.5, the mean marker expression, the number of cells."""
@@ -35,7 +36,7 @@ def neighborhood_sums(xy, feats, seg, radius, closed=False):
             counts[a + i] = mask.sum()
             if mask.any() and rows.shape[1]:
                 with np.errstate(invalid="ignore"):
-                    sums[a + i] = rows[mask].cumsum(axis=0)[-1]
+                    sums[a + i] = np.concatenate([np.zeros((1, rows.shape[1])), rows[mask]]).cumsum(axis=0)[-1]
     return sums, counts
 
 

@@ -1,5 +1,6 @@
 """The case generators of the randomised sweeps (test_gpu_fuzz_parity.py: metric assign / online training;
-test_gpu_fuzz_images.py: K10 - K12; test_gpu_fuzz_preprocessing.py: K2 - K5 and the label kernels) on CPU: the first
+test_gpu_fuzz_images.py: K10 - K12; test_gpu_fuzz_preprocessing.py: K2 - K5 and the label kernels;
+test_gpu_fuzz_neighborhood_sums.py: K24; test_gpu_fuzz_overlays.py: K29; test_gpu_fuzz_embed.py: K30) on CPU: the first
 default run of cases of each -- 12, or the family's class count when that is larger -- lands in every route class it is
 meant to visit, each case's class is the one the library's own rule gives for its parameters, and one seed gives the
 same cases twice.  Where a sweep's reference is a numpy / scipy / pandas statement rather than the oracle, the oracle
@@ -516,3 +517,287 @@ def test_cluster_sums_generator(oracle):
         np.add.at(sums, c["labels"][valid].astype(np.int64) - 1, x[valid])
         assert np.array_equal(ws, sums) and np.array_equal(wc, np.bincount(c["labels"][valid] - 1, minlength=k))
         assert np.abs(ws + c["sums0"]).max() < 2 ** 29                # ... and stay exact on the prefilled tables
+
+
+# ---- K24, K29 (test_gpu_fuzz_neighborhood_sums.py, test_gpu_fuzz_overlays.py) ----------------------------------------
+def _same_value(va, vb, key=""):
+    if isinstance(va, np.ndarray):
+        assert isinstance(vb, np.ndarray) and va.dtype == vb.dtype and va.shape == vb.shape, key
+        assert va.tobytes() == vb.tobytes(), key
+    elif isinstance(va, dict):
+        assert va.keys() == vb.keys(), key
+        for k in va:
+            _same_value(va[k], vb[k], "%s.%s" % (key, k))
+    elif isinstance(va, (list, tuple)):
+        assert len(va) == len(vb), key
+        for k, (a, b) in enumerate(zip(va, vb)):
+            _same_value(a, b, "%s[%d]" % (key, k))
+    else:
+        assert va == vb or (va != va and vb != vb), key
+
+
+def _twice_deep(gen, seed, n):
+    a, b = list(gen(seed, n)), list(gen(seed, n))
+    assert len(a) == len(b) == n
+    _same_value(a, b)
+    return a
+
+
+def test_neighborhood_sums_fold_starts_from_plus_zero():
+    """The statement's fold is a plain float fold from +0.0 in row order (include/pxsom.h): members that are all -0.0 give
+    +0.0, where numpy's own cumulative sum from the first member gives -0.0."""
+    from tests import splda_reference as sr
+    xy = np.zeros((3, 2))
+    feats = np.array([[-0.0, 1e8, -0.0], [-0.0, 1.0, 0.0], [-0.0, -1e8, -0.0]])
+    sums, counts = sr.neighborhood_sums(xy, feats, np.array([0, 3]), 1.0)
+    assert counts.tolist() == [3, 3, 3]
+    for row in sums:
+        for t in range(3):
+            acc = 0.0
+            for v in feats[:, t]:
+                acc = acc + float(v)
+            assert row[t] == acc and np.signbit(row[t]) == np.signbit(acc)
+        assert not np.signbit(row[0]) and not np.signbit(row[2]) and row[1] == 1.0
+    assert np.signbit(feats.cumsum(axis=0)[-1, 0])           # what the fold from the first member gave
+
+
+def test_neighborhood_sums_generator():
+    from tests import splda_reference as sr
+    from tests import test_gpu_fuzz_neighborhood_sums as fn
+    assert fn.NS_CASES == len(fn.NS_CLASSES) == 40 or fq._ENV_CASES is not None
+    cases = _twice_deep(fn.neighborhood_sums_cases, fq.SEED + 60, len(fn.NS_CLASSES))
+    assert {c["cls"] for c in cases} == set(fn.NS_CLASSES)
+    assert {(c["cls"][2], c["cls"][3]) for c in cases} == {(r, f) for r in fn.RADIUS_CLASSES for f in fn.FEAT_CLASSES}
+    assert {c["cls"][0] for c in cases} == {"uniform", "lattice", "clumps", "rational", "tiny_fovs", "one_big"}
+    assert sum(c["cls"][0] == "lattice" and c["cls"][2] == "exact" for c in cases) >= 2
+    sizes = {m for c in cases for m in c["sizes"]}
+    assert {0, 1, 255, 256, 257} <= sizes
+    assert any(m % fn.kBlock % fn.kGroup for m in sizes if m > fn.kBlock), "no last tile that is no multiple of 32"
+    assert {c["n_feat"] for c in cases} >= {0, 1, 7, 8, 9, 16, 17} and max(c["n_feat"] for c in cases) >= 65
+    assert {c["feat_off"] % 2 for c in cases if c["n_feat"]} == {0, 1}            # 8 bytes, and 16
+    order_matters = 0
+    for c in cases:
+        xy, seg, radius = c["xy"], c["seg"], c["radius"]
+        assert seg[0] == 0 and seg[-1] == len(xy) and np.all(np.diff(seg) >= 0) and np.isfinite(xy).all()
+        assert (c["feats"] is None) == (c["n_feat"] == 0)
+        if c["feats"] is not None and c["feats"].size >= 400:      # (a table of a few cells need not hold every kind)
+            f = c["feats"]
+            assert np.isnan(f).any() and np.isposinf(f).any() and (np.signbit(f) & (f == 0)).any()
+            mag = np.abs(f[np.isfinite(f) & (f != 0)])
+            assert mag.min() < 1e-6 and mag.max() > 1e6 and (f < 0).any() and (f > 0).any()
+        layout, _, rcls, _ = c["cls"]
+        if layout == "lattice":                  # exact: the coordinates are integers times the scale
+            k = xy / c["scale"]
+            assert np.array_equal(k, np.rint(k)) and np.array_equal(k * c["scale"], xy)
+        _, lt = sr.neighborhood_sums(xy, None, seg, radius, False)
+        _, le = sr.neighborhood_sums(xy, None, seg, radius, True)
+        a, b = c["big"]
+        if rcls == "zero":
+            assert radius == 0 and not lt.any() and (le >= 1).all()
+        elif rcls == "below_all":                # only the cells on the same centroid
+            same = np.array([np.sum(np.all(xy[int(s):int(e)] == xy[i], axis=1)) for s, e in zip(seg[:-1], seg[1:])
+                             for i in range(int(s), int(e))], dtype=np.int64)
+            assert np.array_equal(lt, same) and np.array_equal(le, same)
+        elif rcls == "ten":                      # about ten in a FOV large enough to hold them: between 5 and 20 on average
+            if b - a >= 40:
+                assert 5 <= lt[a:b].mean() <= 20, (c["cls"], lt[a:b].mean())
+            assert lt.max() <= 60
+        elif rcls == "all":
+            assert np.array_equal(lt, np.repeat(np.diff(seg), np.diff(seg))) and np.array_equal(lt, le)
+        else:                                    # pairs lie exactly at the radius: in under "le", out under "lt"
+            pts = xy[a:b]
+            dx, dy = pts[:, None, 0] - pts[None, :, 0], pts[:, None, 1] - pts[None, :, 1]
+            at = np.sqrt(dx * dx + dy * dy) == radius
+            assert at.sum() >= 2 and np.array_equal(at, at.T), c["cls"]
+            assert np.array_equal((le - lt)[a:b], at.sum(axis=1)), c["cls"]
+            if layout == "lattice":              # the radius is a lattice distance: hypotenuse x step x scale, exactly
+                assert radius / (c["step"] * c["scale"]) in {h[2] for h in fn.LATTICE_HYPOTENUSES}
+                assert at.sum() >= 8
+        if c["feats"] is not None and rcls in ("all", "exact") and b - a >= 40:
+            # only the ascending-row order gives the statement's bits: the members of a row folded in descending order differ
+            sums, _ = sr.neighborhood_sums(xy[a:b], c["feats"][a:b], np.array([0, b - a]), radius, True)
+            members = c["feats"][a:b][sr._mask(xy[a:b], 0, np.float64(radius), True)]
+            with np.errstate(invalid="ignore"):
+                fwd = np.concatenate([np.zeros((1, members.shape[1])), members]).cumsum(axis=0)[-1]
+                rev = np.concatenate([np.zeros((1, members.shape[1])), members[::-1]]).cumsum(axis=0)[-1]
+            assert fq._same_bits(fwd, sums[0])
+            both = np.isfinite(fwd) & np.isfinite(rev)
+            if len(members) >= 8:
+                assert (fwd[both] != rev[both]).any(), c["cls"]
+                order_matters += 1
+    assert order_matters >= 6
+
+
+def test_overlay_generators():
+    from tests import overlay_reference as ovr
+    from tests import test_gpu_fuzz_overlays as fo
+    cases = _twice_deep(fo.overlay_cases, fq.SEED + 70, fq.default_cases(fo.OVERLAY_CLASSES))
+    assert len(cases) == 30
+    assert {(c["cls"]["rgb_off"], c["w"] % 4) for c in cases} == {(a, b) for a in range(4) for b in range(4)}
+    assert {c["cls"]["borders_off"] for c in cases} == {0, 1, 2, 3} == {c["cls"]["in_off"] for c in cases}
+    assert {(c["cls"]["plane"], c["cls"]["seg"]) for c in cases} == {(p, s) for p in fo.PLANE_NP for s in fo.SEG_NP}
+    assert {(c["cls"]["plane"], c["cls"]["range_cls"]) for c in cases} == {(p, r) for p in fo.PLANE_NP for r in fo.RANGE_CLASSES}
+    assert {(b, c["modes"][b]) for c in cases for b in range(3)} == {(b, m) for b in range(3) for m in range(3)}
+    assert {c["alt"] is None for c in cases} == {True, False}
+    assert any(abs(c["h"] - 4) <= 1 for c in cases) and any(abs(c["h"] - 16) <= 1 for c in cases)
+    assert any(abs(c["w"] - 256) <= 3 for c in cases) and any(abs(c["w"] - 512) <= 3 for c in cases)
+    for c in cases:
+        cls = c["cls"]
+        assert c["w"] % 4 == cls["wmod"] and c["seg"].dtype == cls["seg"] and c["seg"].shape == (c["h"], c["w"])
+        if c["alt"] is not None:
+            assert c["alt"].dtype.itemsize != c["seg"].dtype.itemsize
+        b = cls["byte"]
+        lo, hi = c["ranges"][b]
+        mode, plane = c["modes"][b], c["planes"][b]
+        assert plane.dtype == cls["plane"] and not (plane.dtype.kind == "f" and np.isnan(plane).any())
+        assert (mode == ovr.OVERLAY_RESCALE and lo < hi) or (mode == ovr.OVERLAY_CLIP and lo == hi)
+        if cls["range_cls"] == "negative_lo":
+            assert lo < 0 < hi
+        elif cls["range_cls"] == "one_ulp":
+            assert np.float32(lo) == lo and np.float32(hi) == hi and np.nextafter(np.float32(lo), np.float32(np.inf)) == hi
+            if plane.dtype == np.float32:
+                assert (plane == np.float32(lo)).any() and (plane == np.float32(hi)).any()
+        elif cls["range_cls"] == "span_2_31":
+            assert hi - lo > 2.0 ** 31 - 8
+            if plane.dtype == np.int32:
+                assert plane.min() < -2 ** 30 and plane.max() > 2 ** 30
+        elif cls["range_cls"] == "clip_below_0":
+            assert lo == hi < 0 and (ovr.compose(c["planes"], c["modes"], c["ranges"], np.zeros_like(c["seg"]))[..., b] == 0).all()
+        elif cls["range_cls"] == "clip_above_255":
+            assert lo == hi > 255 and (ovr.compose(c["planes"], c["modes"], c["ranges"], np.zeros_like(c["seg"]))[..., b] == 255).all()
+        # compose is what overlay is made of: the percentile ranges of a plane give overlay's bytes
+        if cls["range_cls"] == "percentile":
+            alone = ovr.compose([None, None, plane], [0, 0, mode], [(0, 0), (0, 0), (lo, hi)], c["seg"], c["alt"])
+            assert np.array_equal(alone, ovr.overlay(plane, c["seg"], c["alt"]))
+
+    cases = _twice_deep(fo.colorize_cases, fq.SEED + 71, fq.default_cases(fo.COLORIZE_CLASSES))
+    assert {(c["cls"]["mask_off"], c["cls"]["out_off"]) for c in cases} >= {(a, b) for a in range(4) for b in range(4)}
+    assert {c["route"] for c in cases} == {(a, b) for a in (False, True) for b in (False, True)}
+    assert {(c["cls"]["out_off"], c["mask"].size % 4) for c in cases if not c["cls"]["bad"]} == {(a, b) for a in range(4) for b in range(4)}
+    assert {c["mask"].dtype.type for c in cases} == set(fo.COLORIZE_MASK_NP) and {c["table"].shape[1] for c in cases} == {3, 4}
+    assert {len(c["table"]) for c in cases} >= {1, 2, 255, 256, 70000}
+    assert {c["mask"].dtype.type for c in cases if len(c["table"]) == 70000} >= {np.uint16, np.int32}
+    for c in cases:
+        assert c["route"] == fo.colorize_route(c["cls"]["mask_off"], c["cls"]["out_off"]) == (
+            c["cls"]["mask_off"] == 0, c["cls"]["out_off"] == 0)
+        idx = c["mask"].astype(np.int64)
+        outside = (idx < 0) | (idx >= len(c["table"]))
+        assert outside.any() == c["cls"]["bad"] and (not c["cls"]["bad"] or all(outside[y, x] for y, x in c["bad_at"]))
+        assert (~outside).any()
+    assert sum(c["cls"]["bad"] for c in cases) == 4
+
+    cases = _twice_deep(fo.listq_cases, fq.SEED + 72, fq.default_cases(fo.LISTQ_CLASSES))
+    assert [c["cls"] for c in cases] == list(fo.LISTQ_CLASSES)
+    assert {c["x"].shape[1] for c in cases} >= {1, 47, 48, 49, 97} and {len(c["q"]) for c in cases} == {1, 2, 3, 4}
+    assert {c["keep_mode"] for c in cases} == {0, 1, 2} and any(c["off"] and c["pad"] for c in cases)
+    for c in cases:
+        x, q, mode = c["x"], c["q"], c["keep_mode"]
+        assert x.dtype == np.float32 and all(0 <= v <= 100 for v in q)
+        kept = [fq.quantile_kept(np.ascontiguousarray(x[:, j]), mode) for j in range(x.shape[1])]
+        if c["cls"] in ("m0", "m1", "m2"):
+            assert kept[0].size == int(c["cls"][1])
+        elif c["cls"] == "q_integral":
+            assert (q[0] / 100 * (kept[0].size - 1)) % 1 == 0 and 0 < q[0] < 100
+        elif c["cls"] == "two_values":
+            assert all(np.unique(k).size == 2 for k in kept)
+        elif c["cls"] == "all_equal":
+            assert all(k.size and np.unique(k).size == 1 for k in kept)
+        elif c["cls"] == "dup_straddle":
+            lo = int(np.floor(q[0] / 100 * (x.shape[0] - 1)))
+            assert all(np.sort(k)[lo] == np.sort(k)[lo + 1] for k in kept)
+        elif c["cls"] == "low_byte":
+            assert np.unique(np.abs(x).view(np.uint32) >> 8).size == 1 and np.unique(x.view(np.uint32) & 0xFF).size > 8
+        elif c["cls"] == "mixed_sign":
+            assert (x < 0).any() and (x > 0).any()
+        elif c["cls"] == "subnormals":
+            assert (np.abs(x[x != 0]) < np.finfo(np.float32).tiny).any()
+        # the statement of tests/overlay_reference.py is numpy's own result for a list of q
+        want = fo.listq_reference(x, q, mode)
+        for j, k in enumerate(kept):
+            if k.size:
+                assert np.array_equal(ovr.percentile_listq_f32(k, q), want[:, j]), (c["cls"], j)
+            else:
+                assert np.isnan(want[:, j]).all()
+
+
+# ---- K30 (test_gpu_fuzz_embed.py) --------------------------------------------------------------------------------------
+def test_embed_generators():
+    from tests import test_gpu_fuzz_embed as fe
+    from tests import tsne_reference as ts
+    cases = _twice_deep(fe.sqdist_cases, fq.SEED + 80, fq.default_cases(fe.SQDIST_CLASSES))
+    assert [c["cls"] for c in cases] == list(fe.SQDIST_CLASSES)
+    assert {(c["cls"][0], c["cls"][1]) for c in cases} == {(n, k) for n in fe.SQDIST_N for k in fe.SQDIST_C}
+    assert {(c["cls"][2], c["x"].dtype.type) for c in cases} == {(v, d) for v in fe.SQDIST_VALUES for d in (np.float32, np.float64)}
+    assert {1, 15, 16, 17, 33} <= {c["x"].shape[0] for c in cases} and any(c["x"].shape[0] > 33 for c in cases)
+    for c in cases:
+        x, vcls = c["x"], c["cls"][2]
+        assert x.shape[1] == c["cls"][1] and np.isfinite(x).all()
+        if vcls == "offset":                      # the columns' offsets dwarf the differences
+            assert np.all(np.abs(x).min(axis=0) > x.max(axis=0) - x.min(axis=0)) and np.abs(x).min() > 900
+        elif vcls == "duplicates" and x.shape[0] > 1:
+            d = ts.pair_sqdist_f32(x)
+            assert (d == 0).sum() > x.shape[0]
+        elif vcls == "scale_1e-6":
+            assert np.abs(x).max() < 1e-4
+        elif vcls == "scale_1e6":
+            assert np.abs(x).max() > 1e5 or x.size < 4
+        elif vcls == "integers":
+            assert np.array_equal(x, np.rint(x))
+    cases = _twice_deep(fe.moment_cases, fq.SEED + 81, fq.default_cases(fe.MOMENT_CLASSES))
+    rows = [c["x"].shape[0] for c in cases]
+    assert {65535, 65536, 65537} <= set(rows) and rows.count(1 << 20) == 1 and any(65537 < n <= 70000 for n in rows)
+    assert {(c["x"].shape[1], c["x"].dtype.type) for c in cases} == {(k, d) for k in (2, 3) for d in (np.float32, np.float64)}
+    for c in cases:
+        n = c["x"].shape[0]
+        assert c["trips"] == fe.moment_trips(n) and (c["trips"] >= 2) == (n > 65536)
+    assert fe.moment_trips(1 << 20) == 16 and ((1 << 20) // fe.kMomentRows) * 8 == 32 * 1024
+
+    cases = _twice_deep(fe.affinity_cases, fq.SEED + 82, fq.default_cases(fe.AFFINITY_CLASSES))
+    assert [c["cls"] for c in cases] == list(fe.AFFINITY_CLASSES)
+    assert {(c["cls"][0], c["cls"][1]) for c in cases} == {(d, r) for d in fe.AFFINITY_DATA for r in fe.AFFINITY_ROWS}
+    assert {(c["cls"][0], c["cls"][2]) for c in cases} == {(d, p) for d in fe.AFFINITY_DATA for p in fe.AFFINITY_PERPLEXITY}
+    assert {(c["cls"][1], c["cls"][2]) for c in cases if c["cls"][1] != 2} == {
+        (r, p) for r in fe.AFFINITY_ROWS if r != 2 for p in fe.AFFINITY_PERPLEXITY}
+    rows = {c["d32"].shape[0] for c in cases}
+    assert {2, 3} <= rows and rows & {31, 32, 33} and rows & {63, 64, 65} and rows & {511, 512, 513} and max(rows) <= 600
+    smallest = np.inf
+    for c in cases:
+        n, data, perp = c["d32"].shape[0], c["cls"][0], c["perplexity"]
+        assert c["d32"].dtype == np.float32 and np.array_equal(c["d32"], ts.pair_sqdist_f32(c["x"])) and c["ws_off"] % 2 == 0
+        assert 1.01 <= perp <= max(1.01, 0.98 * (n - 1)) and (n > 2 or perp == 1.01)
+        assert perp == {"low": 1.01, "high": max(1.01, 0.98 * (n - 1))}.get(c["cls"][2], perp)
+        off = c["d32"][~np.eye(n, dtype=bool)]
+        if data == "lattice":
+            assert np.array_equal(c["x"], np.rint(c["x"])) and (n <= 3 or (off == 0).any())
+        elif data == "outliers":
+            assert off.max() > 1e6 * max(np.median(off), 1e-30) or n < 4
+        elif data == "scale_1e-6_f32":
+            assert c["x"].dtype == np.float32 and off.max() < 1e-8
+        elif data == "scale_1e6":
+            assert off.max() > 1e12
+        # no row of the default seed's cases sits within the rounding bound of a branch of its search
+        margins = ts.conditional_p(c["d32"], perp, margin=True)[3]
+        assert margins.min() > 1, (c["cls"], margins.min())
+        smallest = min(smallest, margins.min())
+    assert smallest > 100
+
+    cases = _twice_deep(fe.step_cases, fq.SEED + 83, fq.default_cases(fe.STEP_CLASSES))
+    assert {(c["cls"]["even"], c["cls"]["aligned"], c["cls"]["scale"], c["cls"]["p"]) for c in cases} == {
+        (a, b, s, p) for a in (False, True) for b in (False, True) for s in fe.STEP_SCALES for p in fe.STEP_P}
+    assert {(c["route"], c["cls"]["want_error"], c["cls"]["grad"]) for c in cases} == {
+        (a, b, g) for a in (False, True) for b in (False, True) for g in (False, True)}
+    assert {c["cls"]["e"] for c in cases} == {1.0, 12.0}
+    for c in cases:
+        n, cls, P = len(c["Y"]), c["cls"], c["P"]
+        # VEC exactly when n is even and P is 16-byte aligned: an odd number of doubles into an aligned buffer is 8 mod 16
+        assert (n % 2 == 0) == cls["even"] and (c["p_off"] % 2 == 0) == cls["aligned"]
+        assert c["route"] == fe.step_route(n, c["p_off"]) == (cls["even"] and cls["aligned"])
+        assert np.array_equal(P, P.T) and np.all(np.diag(P) == ts.EPS) and P.min() >= ts.EPS and c["ws_off"] % 2 == 0
+        if cls["p"] == "uniform":
+            assert np.unique(P[~np.eye(n, dtype=bool)]).size == 1
+        elif cls["p"] == "eps_rows":
+            assert (P == ts.EPS).all(axis=1).any()
+        if cls["scale"] == 200.0:
+            assert np.abs(c["Y"]).max() > 1e6
+        else:
+            assert np.abs(c["Y"]).max() < 10 * cls["scale"]

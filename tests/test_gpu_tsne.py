@@ -279,6 +279,50 @@ def test_init_choices(gpu):
         assert np.array_equal(a, b) and a.n_iter_ == 299 and ts.purity(np.asarray(a), lab) == 1.0, kwargs
 
 
+# ---- the driver's stop rules ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(ts.DESCENT_SCRIPTS))
+def test_driver_stop_rules_follow_the_statement(gpu, monkeypatch, name):
+    """som_device.tsne over a stub of tsne_step that copies y_in to y_out and, when asked for the error, writes the script's
+    (KL, gradient norm): n_iter, the KL and the calls per phase equal ts.descend's on the same script (which
+    tests/test_tsne.py pins to sklearn's TSNE._tsne), and the error is asked for on every 50th iteration and on the last
+    of a phase, nowhere else."""
+    from ark_analysis_amd import som_device as sd
+    from ark_analysis_amd.som_device import embedding
+    max_iter, window, kl, zero_grad, want_it, want_calls = ts.DESCENT_SCRIPTS[name]
+    want_calls_seen = []
+
+    def objective(Y, P, e):
+        i = len(want_calls_seen)
+        want_calls_seen.append(e)
+        return {"kl": kl(i), "grad": np.zeros_like(Y) if i in zero_grad else np.full_like(Y, 1e-3)}
+    monkeypatch.setattr(ts, "objective", objective)
+    _, want_kl, it = ts.descend(None, np.zeros((8, 2)), max_iter=max_iter, n_iter_without_progress=window)
+    assert it == want_it
+
+    calls = []
+
+    def stub(P, y_in, y_out, update, gains, exaggeration, momentum, learning_rate, min_gain=0.01, error=None, grad=None,
+             workspace=None):
+        i = len(calls)
+        calls.append((exaggeration, momentum, error is not None))
+        assert learning_rate == 50.0 and min_gain == 0.01 and grad is None and workspace is not None
+        assert y_in.data_ptr() != y_out.data_ptr()
+        # a phase starts from zero updates and unit gains, which the stub leaves as they are
+        assert not bool(update.any()) and bool((gains == 1.0).all())
+        y_out.copy_(y_in)
+        if error is not None:
+            error.copy_(torch.tensor([kl(i), 0.0 if i in zero_grad else 1.0], dtype=torch.float64))
+    monkeypatch.setattr(embedding, "tsne_step", stub)
+    y0 = _up(np.random.RandomState(1).standard_normal((8, 2)), gpu)
+    res = sd.tsne(torch.zeros((8, 8), dtype=torch.float64, device=gpu), y0, max_iter=max_iter, n_iter_without_progress=window)
+    assert res.n_iter == want_it and res.kl_divergence == want_kl
+    assert [c[0] for c in calls] == want_calls_seen
+    assert [c[:2] for c in calls] == [(12.0, 0.5)] * want_calls[0] + [(1.0, 0.8)] * want_calls[1]
+    ends = [ts.EXPLORATION_ITER] * want_calls[0] + [max_iter] * want_calls[1]
+    assert [c[2] for c in calls] == [ts.asks_error(i, end) for i, end in enumerate(ends)]
+    assert torch.equal(res.embedding, y0) and res.embedding.data_ptr() != y0.data_ptr()
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------
 def test_refusals(gpu, monkeypatch):
     from ark_analysis_amd import som_device as sd

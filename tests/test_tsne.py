@@ -106,6 +106,61 @@ def test_descent_loop_follows_sklearns_schedule(monkeypatch):
     assert it == 299 and calls == [12.0] * 250 + [1.0] * 50 and kl == 1.0 / 300
 
 
+def _sklearn_on_script(monkeypatch, max_iter, window, kl, zero_grad):
+    """TSNE._tsne itself with _kl_divergence replaced by the script -> (n_iter_, kl_divergence_, [(exaggeration,
+    compute_error)] per objective call).  The exaggeration is read off P, which _tsne scales in place around phase 1."""
+    calls = []
+
+    def scripted(params, P, degrees_of_freedom, n_samples, n_components, skip_num_points=0, compute_error=True):
+        i = len(calls)
+        calls.append((float(P[0]), bool(compute_error)))
+        grad = np.zeros_like(params) if i in zero_grad else np.full_like(params, 1e-3)
+        return (kl(i) if compute_error else np.nan), grad
+    monkeypatch.setattr(_t_sne, "_kl_divergence", scripted)
+    est = _t_sne.TSNE(method="exact", max_iter=max_iter, n_iter_without_progress=window)
+    est.learning_rate_ = 50.0
+    est._tsne(np.ones(1), 1, 8, np.zeros((8, 2)))
+    return est.n_iter_, est.kl_divergence_, calls
+
+
+def _statement_on_script(monkeypatch, max_iter, window, kl, zero_grad):
+    calls = []
+
+    def objective(Y, P, e):
+        i = len(calls)
+        calls.append(e)
+        return {"kl": kl(i), "grad": np.zeros_like(Y) if i in zero_grad else np.full_like(Y, 1e-3)}
+    monkeypatch.setattr(ts, "objective", objective)
+    Y, got_kl, it = ts.descend(None, np.zeros((8, 2)), max_iter=max_iter, n_iter_without_progress=window)
+    return it, got_kl, calls
+
+
+@pytest.mark.parametrize("name", sorted(ts.DESCENT_SCRIPTS))
+def test_descent_stop_rules_equal_sklearn(monkeypatch, name):
+    """Both early exits, the restart of phase 2 one past a stopped phase 1 and the fall-through, each on a scripted
+    objective: the statement's loop and sklearn's TSNE._tsne give the same n_iter, the same KL and the same number of
+    objective calls per phase, and both give what the rules say by hand (tests/tsne_reference.py DESCENT_SCRIPTS)."""
+    max_iter, window, kl, zero_grad, want_it, want_calls = ts.DESCENT_SCRIPTS[name]
+    sk_it, sk_kl, sk_calls = _sklearn_on_script(monkeypatch, max_iter, window, kl, zero_grad)
+    it, got_kl, calls = _statement_on_script(monkeypatch, max_iter, window, kl, zero_grad)
+    per_phase = (calls.count(12.0), calls.count(1.0))
+    assert (sk_it, ([c[0] for c in sk_calls].count(12.0), [c[0] for c in sk_calls].count(1.0))) == (want_it, want_calls)
+    assert (it, per_phase) == (want_it, want_calls)
+    assert calls == [c[0] for c in sk_calls]
+    # sklearn asks for the error on every 50th iteration and on the last one a phase can reach, nowhere else
+    ends = [ts.EXPLORATION_ITER] * want_calls[0] + [max_iter] * want_calls[1]
+    first2 = want_it + 1 - want_calls[1]
+    index = list(range(want_calls[0])) + list(range(first2, first2 + want_calls[1]))
+    assert [c[1] for c in sk_calls] == [ts.asks_error(i, end) for i, end in zip(index, ends)]
+    if want_calls[1] == 0:
+        # the one place where the statement leaves sklearn on purpose (DESIGN.md "K30", Driver): a second phase without an
+        # iteration returns _gradient_descent's initial error, the largest float, as kl_divergence_; the statement and the
+        # device driver report the last error computed, that of iteration 249
+        assert sk_kl == np.finfo(np.float64).max and got_kl == kl(ts.EXPLORATION_ITER - 1)
+    else:
+        assert got_kl == sk_kl == kl(want_it)
+
+
 def test_pca_scores_equal_sklearn():
     for n, c, seed, dtype in ((64, 2, 0, np.float64), (257, 22, 1, np.float32), (300, 100, 2, np.float64)):
         r = np.random.RandomState(seed)

@@ -69,10 +69,24 @@ def row_entropy_diff(drow, i, beta, perplexity):
     return np.log(s) + beta * (d * (p / s)).sum() - np.log(float(np.float32(perplexity)))
 
 
-def conditional_p(d32, perplexity):
-    """sklearn/manifold/_utils.pyx _binary_search_perplexity on a dense float32 matrix -> (P, beta, steps)."""
+def conditional_p(d32, perplexity, margin=False):
+    """sklearn/manifold/_utils.pyx _binary_search_perplexity on a dense float32 matrix -> (P, beta, steps), with ``margin``
+    also a per-row margin [n].
+
+    The margin says how far a row's search is from taking another path on an implementation that rounds differently.  The
+    search branches on diff = log s + beta * sum_j d_j p_j - log perplexity twice: on |diff| <= tol (stop) and on the sign of
+    diff (which bound moves).  Another path needs |diff| to cross tol or diff to cross 0, so at one evaluation the distance
+    to a branch is min(|diff|, ||diff| - tol|).  The rounding bound E of diff at that evaluation, U = 2^-53: s is a sum of
+    n - 1 terms exp(-d_j beta), each with a relative error of a few U (the product, the exponential; a term whose argument
+    is large enough for the product's error to matter weighs x exp(-x) <= 0.37 of that), so s carries at most (n + 16) U
+    relatively, log s that much absolutely plus U |log s| of its own; beta * sum d p is a sum of n - 1 non-negative terms
+    over the same s: (n + 16) U of its value; log perplexity one rounding, U |log perplexity|.  Together at most
+    (n + 16) U (1 + |log s| + beta sum d p + |log perplexity|) for one implementation, twice that between two:
+        E = 2 (n + 16) U (1 + |log s| + beta * sum d p + |log perplexity|).
+    The row's margin is the smallest min(|diff|, ||diff| - tol|) / E over its evaluations: above 1, no rounding within
+    the bound changes beta or steps."""
     n = d32.shape[0]
-    P, betas, steps = np.zeros((n, n)), np.zeros(n), np.zeros(n, np.int32)
+    P, betas, steps, margins = np.zeros((n, n)), np.zeros(n), np.zeros(n, np.int32), np.full(n, np.inf)
     tol, tiny = float(np.float32(1e-5)), float(np.float32(1e-8))
     target = np.log(float(np.float32(perplexity)))
     d = d32.astype(np.float64)
@@ -86,7 +100,11 @@ def conditional_p(d32, perplexity):
             if s == 0.0:
                 s = tiny
             p = p / s
-            diff = np.log(s) + b * (d[i] * p).sum() - target
+            energy = b * (d[i] * p).sum()
+            diff = np.log(s) + energy - target
+            if margin:
+                e = 2 * (n + 16) * 2.0 ** -53 * (1 + abs(np.log(s)) + energy + abs(target))
+                margins[i] = min(margins[i], min(abs(diff), abs(abs(diff) - tol)) / e)
             if abs(diff) <= tol:
                 break
             if diff > 0:
@@ -96,7 +114,7 @@ def conditional_p(d32, perplexity):
                 hi = b
                 b = b / 2 if lo == -np.inf else (b + lo) / 2
         P[i], betas[i], steps[i] = p, b, it
-    return P, betas, steps
+    return (P, betas, steps, margins) if margin else (P, betas, steps)
 
 
 def joint_p(cond):
@@ -183,6 +201,48 @@ def descend(P, Y0, max_iter=1000, n_iter_without_progress=300):
     if it < EXPLORATION_ITER or max_iter - EXPLORATION_ITER > 0:
         it = phase(it + 1, max_iter, 0.8, 1.0, n_iter_without_progress)
     return state["Y"], float(state["kl"]), it
+
+
+# ---- scripted objectives for the stop rules ------------------------------------------------------------------------------
+# The descent is chaotic, so its stop rules are tested on an objective that ignores Y: call number i (which is iteration i,
+# since the second phase starts one past the first phase's last iteration) returns kl(i) and a gradient that is zero at the
+# iterations listed in ``zero_grad`` and 1e-3 everywhere else.  Each entry: name -> (max_iter, n_iter_without_progress, kl,
+# zero_grad, n_iter expected, calls in the two phases expected) -- the expectations worked out by hand from sklearn's rules:
+# a check at every i with (i + 1) % 50 == 0; kl < best moves best_it to i, else i - best_it > window stops; then a gradient
+# norm <= 1e-7 stops; phase 2 runs from the first phase's last iteration + 1 with best_it set to its first iteration.
+def _falling(i):
+    return 1.0 / (i + 1)
+
+
+def _flat_from_300(i):
+    return 1.0 / (i + 1) if i < 300 else 1.0        # the best check is i = 299
+
+
+DESCENT_SCRIPTS = {
+    "no_stop": (1000, 300, _falling, (), 999, (250, 750)),
+    # a zero gradient stops only where it is looked at: 123, 301 and 310 are no checks
+    "grad_stop_phase2": (1000, 300, _falling, (123, 301, 310, 449), 449, (250, 200)),
+    "grad_stop_at_49": (1000, 300, _falling, (49,), 999, (50, 950)),
+    "grad_stop_at_49_then_99": (1000, 300, _falling, (49, 99), 99, (50, 50)),
+    "grad_stop_at_49_max_250": (250, 300, _falling, (49,), 249, (50, 200)),
+    # 349 - 299 = 50 is not past a window of 50; 399 - 299 is
+    "window_50": (1000, 50, _flat_from_300, (), 399, (250, 150)),
+    "window_100": (1000, 100, _flat_from_300, (), 449, (250, 200)),
+    "window_300": (1000, 300, _flat_from_300, (), 649, (250, 400)),
+    # ends at max_iter on the check where i - best_it equals the window
+    "window_300_max_600": (600, 300, _flat_from_300, (), 599, (250, 350)),
+    # a KL equal to the best is no progress: best_it stays 299 (49 in the first phase, whose window of 250 cannot run out)
+    "kl_equal_best": (1000, 50, lambda i: 0.5, (), 399, (250, 150)),
+    # progress at 449 restarts the window
+    "progress_restarts_window": (1000, 100, lambda i: 1e-4 if i == 449 else _flat_from_300(i), (), 599, (250, 350)),
+    "max_iter_250": (250, 300, _falling, (), 250, (250, 0)),
+    "max_iter_251": (251, 300, _falling, (), 250, (250, 1)),
+}
+
+
+def asks_error(i, phase_end):
+    """Whether iteration i of a phase that ends before ``phase_end`` computes the error: every 50th and the phase's last."""
+    return (i + 1) % ITER_CHECK == 0 or i == phase_end - 1
 
 
 def embed(values, algorithm, random_state=None, perplexity=30.0, max_iter=1000, init="pca"):
